@@ -14,7 +14,12 @@ results {qid, n_tokens, tokens, top10_tok, top10_prob} are gathered once at the 
 `--gpus N` with N > 1 and no torchrun environment re-launches itself as N ranks (python -m torch.distributed.run on 127.0.0.1);
 under torchrun (the driver's launch) it reads RANK / LOCAL_RANK / WORLD_SIZE.  n_gpus on the line is the real world size.
 
-Extra objects on the line:
+A plain run does only what the headline needs: set-up, `--warmup` untimed steps, `--steps` timed steps, the line.  ms_per_step = the wall
+time of the timed steps / --steps.  `--dump-outputs DIR` writes the gathered per-question results of the last timed step as DIR/<name>.npy
+(`dump_outputs`); the inputs are seeded, so two builds can be compared output for output.  `--choices-out PATH` writes the GEMM tuner's
+picks of the run as JSON (the source of llava-align_amd/gemm_choices_mi355x.json).
+
+Extra objects on the line, measured only with `--full` (the baselines among them also need no `--no-baselines`):
   roofline      the fused contrastive sampling kernel (the kernel north_star prices) at B=4096 rows, HIP events on the launch
                 stream: frac = SURVEY §8d algorithmic bytes / time / 8 TB/s, frac_traffic = the bytes the launch really moves
                 (computed from the survivor count of the same inputs: c is only read where a candidate survives the beta-mask)
@@ -53,18 +58,29 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measu
 N_NEW = 64
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--questions", type=int, default=768, help="questions per generate() batch per GPU (6 per image); 768 = 1,536 decode rows, ~190 GB of KV pools + weights")
     ap.add_argument("--model", default="llava-1.5-7b")
-    ap.add_argument("--no-baselines", action="store_true")
+    ap.add_argument("--no-baselines", action="store_true", help="with --full: skip the baseline and other-config legs")
     ap.add_argument("--strong", type=int, default=0, metavar="N_QUESTIONS",
                     help="strong-scaling mode: ONE seeded list of N questions (6 per image) split over the ranks by shard.get_chunk "
                          "(the reference's contiguous ceil-chunks, whole image groups), EOS on, ragged results gathered once")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: fused-kernel rooflines, decode-only rate, pope_eos, pcie_inclusive, "
+                         "single_question and (unless --no-baselines) the GPU / CPU baselines, the other BASELINE configs, batch_invariant and fp16")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the gathered results of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--choices-out", metavar="PATH", default=None, help="write the GEMM tuner's picks of this run as JSON")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if a.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return a
 
 
 def maybe_relaunch(a):
@@ -99,6 +115,32 @@ def pope_prompts(n_img, per_img=6, seed=1234, vocab=32000, n_sys=35, txt=(19, 29
             ids.append(torch.tensor(sys_tok + [-200] + t))
             imgs.append(im)
     return ids, imgs
+
+
+DUMP_MAX_BYTES = 60_000_000            # under 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, res, max_bytes=DUMP_MAX_BYTES):
+    """`--dump-outputs DIR`: the per-question payload the timed step hands back (shard.gather_results of the last step, every rank's
+    questions) as DIR/<name>.npy - tokens, n_tokens, top_tok as float64 (token ids are exact), top_prob as float32.  When that exceeds
+    `max_bytes`, a fixed seeded sample of the question rows is written instead, their indices in DIR/rows.npy."""
+    import numpy as np
+    arrs = {}
+    for k in ("tokens", "n_tokens", "top_tok", "top_prob"):
+        if res.get(k) is not None:
+            v = res[k].detach().cpu().numpy()
+            arrs[k] = v.astype(np.float32 if v.dtype == np.float32 else np.float64)
+    n = len(arrs["tokens"])
+    total = sum(v.nbytes for v in arrs.values())
+    if total > max_bytes:
+        keep = max(1, max_bytes // (total // n + 8))                        # + 8 bytes per row for rows.npy
+        rows = np.sort(np.random.default_rng(0).choice(n, size=min(keep, n), replace=False))
+        arrs = {k: v[rows] for k, v in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(path, f"{k}.npy"), v)
+    return sorted(arrs)
 
 
 # ------------------------------------------------------------------ fused-kernel roofline leg
@@ -765,6 +807,8 @@ def run_strong(a, eng, dev, rank, world):
         dt = t.item()
     if rank == 0:
         assert res["count"].tolist() == [1] * N, "the shards do not partition the question list"
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, res)
         total_tokens = int(res["n_tokens"].sum().item())
         print(json.dumps({"metric": "decode tokens/sec (VDD dual-pass) LLaVA-1.5-7B POPE", "value": round(total_tokens * a.steps / dt, 1), "unit": "tokens/s",
                           "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2), "higher_is_better": True,
@@ -823,7 +867,7 @@ def main():
 
     tiny = a.model.startswith("tiny")
     roof = roof_extra = None
-    if rank == 0 and not tiny and not a.strong:
+    if a.full and rank == 0 and not tiny and not a.strong:
         roof = kernel_point(dev, 4096, 32000)
         roof_extra = [kernel_point(dev, 4096, 32000, beta=1e-6, iters=50), kernel_point(dev, 1024, 151936, iters=50),
                       kernel_point(dev, 1024, 151936, scores=False, iters=50),
@@ -877,33 +921,35 @@ def main():
     assert res["tokens"].shape == (world * Q, n_new) and res["top_prob"].shape == (world * Q, 10)
 
     if rank == 0:
-        # decode-only rate: same batch, 2 new tokens (prefill + 1 decode step) subtracted
-        kw2 = dict(kw, max_new_tokens=2)
-        eng.generate(ids, **kw2); eng.generate(ids, **kw2)
-        torch.cuda.synchronize(dev)
-        t1 = time.perf_counter(); o2 = eng.generate(ids, **kw2); torch.cuda.synchronize(dev); t_pre = time.perf_counter() - t1
-        ms_step = dt / a.steps * 1e3
-        ms_decode = (dt / a.steps - t_pre) / (n_new - 2) * 1e3
-        wbytes = eng.w.lm_stream_bytes()
-        if roof is not None:
-            roof["traffic_pmc"] = pmc_traffic()
         line = {"metric": "decode tokens/sec (VDD dual-pass) LLaVA-1.5-7B POPE", "value": round(world * Q * n_new * a.steps / dt, 1),
-                "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_step, 2),
+                "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2),
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
                 "config": {"workload": f"LLaVA-1.5-7B shapes (synthetic N(0,0.02) weights, lm_head x4), POPE-like: {Q} questions/GPU = {n_img} images x 6, "
                                        f"prompt 35 sys + 576 image + 19..28 text tokens, use_dd_unk, cd_alpha=1, cd_beta=0.1, T=0.2, "
                                        f"{n_new} new tokens (no EOS), ViT + both-branch prefill + decode + step-0 top-10 all inside the timed step",
                            "questions_per_gpu": Q, "max_new_tokens": n_new, "parallelism": f"dp{world}"},
                 "tokens_per_s_per_gpu": round(Q * n_new * a.steps / dt, 1),
-                "decode_only_tokens_per_s_per_gpu": round(Q / (ms_decode * 1e-3), 1),
-                "prefill_plus_first_token_s": round(t_pre, 4),
-                "decode_step": {"ms": round(ms_decode, 3), "rows": 2 * Q, "lm_weight_bytes": wbytes,
-                                "weight_stream_GBs": round(wbytes / (ms_decode * 1e-3) / 1e9, 1),
-                                "note": "per step the LM weights are streamed once for all rows; KV reads come on top"},
                 "hbm_peak_GB": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1),
                 "prefill_tokens": out.stats["prefill_tokens"], "unshared_prefill_tokens": out.stats["unshared_prefill_tokens"],
                 "gemm": "hand-written MFMA kernels for every projection (csrc/vdd_gemm.hip; no hipBLASLt on the path)",
-                "roofline": roof, "roofline_extra": roof_extra}
+                "roofline": roof, "roofline_extra": roof_extra, "cpu_baseline": None}
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, res)
+    if rank == 0 and a.full:
+        # decode-only rate: same batch, 2 new tokens (prefill + 1 decode step) subtracted
+        kw2 = dict(kw, max_new_tokens=2)
+        eng.generate(ids, **kw2); eng.generate(ids, **kw2)
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter(); o2 = eng.generate(ids, **kw2); torch.cuda.synchronize(dev); t_pre = time.perf_counter() - t1
+        ms_decode = (dt / a.steps - t_pre) / (n_new - 2) * 1e3
+        line["decode_only_tokens_per_s_per_gpu"] = round(Q / (ms_decode * 1e-3), 1)
+        line["prefill_plus_first_token_s"] = round(t_pre, 4)
+        wbytes = eng.w.lm_stream_bytes()
+        line["decode_step"] = {"ms": round(ms_decode, 3), "rows": 2 * Q, "lm_weight_bytes": wbytes,
+                               "weight_stream_GBs": round(wbytes / (ms_decode * 1e-3) / 1e9, 1),
+                               "note": "per step the LM weights are streamed once for all rows; KV reads come on top"}
+        if roof is not None:
+            roof["traffic_pmc"] = pmc_traffic()
         # POPE proper: answers are 1-2 tokens, then EOS.  The EOS ids are the second tokens this very (seeded) batch emits, so every
         # question stops through the kernel's EOS / pad / unfinished logic after 1 or 2 tokens; max_new_tokens stays 64.
         eos = sorted(set(o2.tokens[:, 1].tolist()))
@@ -983,12 +1029,11 @@ def main():
             torch.cuda.empty_cache()
             _leg(line, "config3", bench_config3, dev)
             _leg(line, "config4", bench_config4, dev)
-        else:
-            line["cpu_baseline"] = None
+    if rank == 0:
         line["collective_backend"] = (os.environ.get("VDD_DIST_BACKEND", "nccl") if use_dist else None)
-        if os.path.isdir(os.path.join(ROOT, "gpurun_out")):        # the tuner's picks of this run (source of llava-align_amd/gemm_choices_mi355x.json)
+        if a.choices_out:                                  # the tuner's picks of this run (source of llava-align_amd/gemm_choices_mi355x.json)
             from llava_align_amd import ops
-            with open(os.path.join(ROOT, "gpurun_out", "gemm_choices_bench.json"), "w") as f:
+            with open(a.choices_out, "w") as f:
                 json.dump({"device": torch.cuda.get_device_name(dev), "choices": ops.gemm_choices_export()}, f, indent=0, sort_keys=True)
         print(json.dumps(line))
     if use_dist:

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +22,7 @@ def _run(args, env_extra):
 
 
 def test_bench_gpus_2_launches_two_ranks_itself():
-    line = _run(["--gpus", "2", "--model", "tiny", "--questions", "12", "--steps", "1", "--warmup", "1", "--no-baselines"],
+    line = _run(["--gpus", "2", "--model", "tiny", "--questions", "12", "--steps", "1", "--warmup", "1", "--full", "--no-baselines"],
                 {"VDD_FORCE_DEVICE": "0", "VDD_DIST_BACKEND": "gloo"})
     assert line["n_gpus"] == 2 and line["config"]["parallelism"] == "dp2" and line["scaling"] == "weak"
     assert line["value"] > 0 and abs(line["value"] - 2 * line["tokens_per_s_per_gpu"]) <= 0.02 * line["value"]
@@ -54,3 +55,23 @@ def test_bench_result_gather_through_rccl_at_world_size_one():
     line = _run(["--model", "tiny", "--questions", "12", "--steps", "1", "--warmup", "1", "--no-baselines"],
                 {"VDD_FORCE_DIST": "1", "VDD_DIST_BACKEND": "nccl", "MASTER_PORT": "29541", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert line["collective_backend"] == "nccl" and line["n_gpus"] == 1 and line["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_legs(tmp_path):
+    """A plain run times exactly --steps steps and measures nothing else; --full adds the extra legs.  --dump-outputs writes the same
+    results in both (seeded inputs, the tuner's choices shared through one cache file)."""
+    env = {"VDD_GEMM_CHOICES": str(tmp_path / "choices.json")}
+    args = ["--model", "tiny", "--questions", "12", "--steps", "2", "--warmup", "1"]
+    plain = _run(args + ["--dump-outputs", str(tmp_path / "plain")], env)
+    full = _run(args + ["--full", "--no-baselines", "--dump-outputs", str(tmp_path / "full")], env)
+    for line in (plain, full):
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "tokens/s" and line["dtype"] == "bf16"
+        assert abs(line["value"] - 12 * 16 * 1e3 / line["ms_per_step"]) <= 0.02 * line["value"]
+    assert not {"pope_eos", "decode_step", "pcie_inclusive"} & set(plain)
+    assert {"pope_eos", "decode_step", "pcie_inclusive"} <= set(full)
+    for name in ("tokens", "n_tokens", "top_tok", "top_prob"):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == 12
+        assert np.array_equal(a, b), name
+    p = np.load(tmp_path / "plain" / "top_prob.npy")
+    assert p.min() >= 0 and p.sum(1).max() <= 1.01                     # step-0 top-10 probabilities, rounded to the model's bf16

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile set (run on the GPU box through gpurun from the repo root): writes everything under gpurun_out/prof/.
-#   1. rocprofv3 --kernel-trace --stats of `python bench.py --no-baselines` (the summary the bench line's numbers come from)
+#   1. rocprofv3 --kernel-trace --stats of `python bench.py --full --no-baselines` (the summary the bench line's numbers come from)
 #   2. PMC FETCH_SIZE / WRITE_SIZE of the fused sampling kernel at the roofline shape (SEPARATE passes, counters only)
 #   3. PMC MfmaUtil of the hand-written GEMM at decode / prefill sizes, the flash attention and the MFMA prefix pass
 set -u
@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof
 mkdir -p $OUT
 # hard limits on every rocprofv3 run: when the traced process aborts, rocprofv3 keeps waiting for it (one such run cost 36 GPU-minutes)
-timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python bench.py --no-baselines > $OUT/bench_line.json 2> $OUT/bench.err
+timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python bench.py --full --no-baselines > $OUT/bench_line.json 2> $OUT/bench.err
 [ -s $OUT/bench_line.json ] || { echo "bench.py under rocprofv3 produced no line (see $OUT/bench.err)"; exit 1; }
 CSV=$(find $OUT/trace -name '*kernel_trace.csv' | head -1)
 python tools/trace_median.py "$CSV" 45 > $OUT/kernel_medians.txt
