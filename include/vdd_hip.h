@@ -340,6 +340,12 @@ int vdd_add(const void* a, const void* b, void* out, int64_t n, int dtype, void*
 /* CLIP ViT LayerNorm (with bias); d % 8 == 0, d <= 4096. */
 int vdd_layernorm(const void* x, const void* w, const void* b, void* y, int M, int d, float eps, int dtype, void* hip_stream);
 
+/* LayerNorm with position tables (Qwen-VL ViT ln_pre and resampler ln_kv, experiments/Qwen_VL/visual.py:142-151,396-398), one row per
+ * block: x' = x + pos_in[r mod T] rounded to the storage type (pos_in may be NULL), y = LN(x'), and with pos_out != NULL a second output
+ * y2 = y + pos_out[r mod T] (rounded).  pos tables [T, d]; d % 8 == 0, d <= 4096.  y equals vdd_layernorm(vdd_add(x, pos_in)) bit for bit. */
+int vdd_layernorm_pos(const void* x, const void* pos_in, const void* pos_out, const void* w, const void* b, void* y, void* y2, int M, int d, int T,
+                      float eps, int dtype, void* hip_stream);
+
 /* y = act(x + bias): act 0 none, 1 quick_gelu (CLIP MLP), 2 gelu-erf (mlp2x_gelu projector, builder.py:33-46). */
 int vdd_bias_act(const void* x, const void* bias, void* y, int64_t M, int d, int act, int dtype, void* hip_stream);
 

@@ -110,21 +110,56 @@ def load_llava(model_path: str, device, dtype=torch.float16, vision_tower: Optio
     return eng, load_tokenizer(model_path), CLIPImageProcessor.from_pretrained(proc_dir)
 
 
-def qwen_embed_prompt(model, tokenize, device, keep_images: int = 16):
+def qwen_embed_prompt(model, tokenize, device, keep_images: int = 16, tower=None):
     """The Qwen front-end the drivers call (mme_driver.qwen_mme_inputs, qwen_driver.run_qwen_pope): `embed_prompt(text, image)` -> [T, d] for
     prompts without an <img> span (image = None), else ([T, d], n_shared) with n_shared = the rows up to and including </img>.  image: a path
     string (the tower reads the file the prompt spells out, modeling_qwen.py:567-568) or a [3, S, S] tensor (`images=`, :565-566); the tower's
     rows for the last `keep_images` distinct tensor OBJECTS are kept, so the six POPE questions about one image cost one ViT pass (the
-    reference: one per generate() call).  tokenize(text) -> ids."""
+    reference: one per generate() call).  tokenize(text) -> ids.
+    tower: a qwen_visual.QwenVisualTower - image tensors, and path strings after the model's own `visual.image_transform` of the file, then
+    go through the native tower instead of `model.transformer.visual`, and the callable also offers `encode_batch(images)`: the distinct
+    images of a list not kept yet go through the tower in ONE call (chunked inside), their rows kept under the keys embed_prompt looks up
+    (tensor objects; path strings).  The rows of one encode_batch call are all kept, whatever keep_images says."""
     from .hf_adapter import qwen_spliced_embeddings
     start = int(model.config.visual["image_start_id"])
-    kept: Dict[int, tuple] = {}                                   # id(tensor) -> (tensor, rows): holding the tensor keeps its id unique
+    kept: Dict[object, tuple] = {}                               # id(tensor) / path -> (image, rows): holding the tensor keeps its id unique
+    key = lambda image: image if isinstance(image, str) else id(image)
+
+    def pixels(image):
+        if torch.is_tensor(image):
+            return image.to(device)
+        from PIL import Image
+        return model.transformer.visual.image_transform(Image.open(image).convert("RGB")).to(device)
+
+    @torch.no_grad()
+    def encode_batch(images):
+        images = [im for im in images if im is not None]
+        fresh, batch = [], set()
+        for im in images:
+            k = key(im)
+            if k in batch:
+                continue
+            batch.add(k)
+            if k in kept:
+                kept[k] = kept.pop(k)                             # most recent last: evicted after everything older
+            else:
+                fresh.append(im)
+        if fresh:
+            rows = tower(torch.stack([pixels(im) for im in fresh]))
+            for i, im in enumerate(fresh):
+                kept[key(im)] = (im, rows[i:i + 1])
+        while len(kept) > max(keep_images, len(batch)):
+            kept.pop(next(iter(kept)))
 
     @torch.no_grad()
     def embed_prompt(text, image):
         ids = torch.tensor([tokenize(text)], device=device)
         feats = None
-        if torch.is_tensor(image):
+        if tower is not None and image is not None:
+            if key(image) not in kept:
+                encode_batch([image])
+            feats = kept[key(image)][1]
+        elif torch.is_tensor(image):
             hit = kept.get(id(image))
             if hit is None:
                 if len(kept) >= keep_images:
@@ -135,17 +170,21 @@ def qwen_embed_prompt(model, tokenize, device, keep_images: int = 16):
         if image is None:
             return e
         return e, int((ids[0] == start + 1).nonzero()[0]) + 1
+    if tower is not None:
+        embed_prompt.encode_batch = encode_batch
     return embed_prompt
 
 
-def load_qwen(model_path: str, device, dtype=torch.bfloat16, use_graph: bool = True):
+def load_qwen(model_path: str, device, dtype=torch.bfloat16, use_graph: bool = True, native_visual: bool = False):
     """-> (engine, tokenizer, HF model, embed_prompt) of a Qwen-VL directory, as the reference's drivers load it
     (`AutoTokenizer / QWenLMHeadModel.from_pretrained(model_path, trust_remote_code=True)`, MME/run_qwen.py:146-157, qwen_calibrate.py:75-86:
     the caller's environment must provide what modeling_qwen.py imports).  The language model runs natively (hf_adapter.lm_weights_from_hf);
     the ViT + resampler stay the model's own `transformer.visual` behind
     `embed_prompt(text, image) -> [T, d]` or `([T, d], n_shared)`: image = None for prompts without an <img> span, a path string (the tower
     reads the file the prompt spells out, modeling_qwen.py:567-568) or a [3, S, S] tensor (`images=`, :565-566); n_shared = the rows up to and
-    including </img>, which every prompt about the same image starts with."""
+    including </img>, which every prompt about the same image starts with.
+    native_visual: the ViT + resampler run on the package's kernels instead (qwen_visual.QwenVisualTower over the model's own
+    `transformer.visual` weights); embed_prompt then also offers `encode_batch(images)`, which the drivers call per batch."""
     from transformers import AutoModelForCausalLM, AutoTokenizer
     from .hf_adapter import lm_config_from_hf, lm_weights_from_hf, qwen_spliced_embeddings
     tok = AutoTokenizer.from_pretrained(model_path, trust_remote_code=True)
@@ -154,7 +193,11 @@ def load_qwen(model_path: str, device, dtype=torch.bfloat16, use_graph: bool = T
     model = AutoModelForCausalLM.from_pretrained(model_path, trust_remote_code=True, torch_dtype=dtype).to(device).eval()
     cfg = lm_config_from_hf(model)
     eng = VddLlavaEngine(cfg, weights=lm_weights_from_hf(model, cfg), device=device, use_graph=use_graph)
-    embed_prompt = qwen_embed_prompt(model, lambda text: tok(text).input_ids, device)
+    tower = None
+    if native_visual:
+        from .qwen_visual import QwenVisualTower, QwenVisualWeights
+        tower = QwenVisualTower(QwenVisualWeights.from_hf(model))
+    embed_prompt = qwen_embed_prompt(model, lambda text: tok(text).input_ids, device, tower=tower)
     return eng, tok, model, embed_prompt
 
 

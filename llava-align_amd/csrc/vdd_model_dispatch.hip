@@ -99,6 +99,9 @@ VDD_MODEL_FN(vdd_vit_qkv_split,
              VDD_P(qkv, q, k_cache, v_cache, n, T, H, D, slot_stride, t_max, parts))
 VDD_MODEL_FN(vdd_add, VDD_P(const void* a, const void* b, void* out, int64_t n), VDD_P(a, b, out, n))
 VDD_MODEL_FN(vdd_layernorm, VDD_P(const void* x, const void* w, const void* b, void* y, int M, int d, float eps), VDD_P(x, w, b, y, M, d, eps))
+VDD_MODEL_FN(vdd_layernorm_pos,
+             VDD_P(const void* x, const void* pos_in, const void* pos_out, const void* w, const void* b, void* y, void* y2, int M, int d, int T, float eps),
+             VDD_P(x, pos_in, pos_out, w, b, y, y2, M, d, T, eps))
 VDD_MODEL_FN(vdd_bias_act, VDD_P(const void* x, const void* bias, void* y, int64_t M, int d, int act), VDD_P(x, bias, y, M, d, act))
 
 // workspace sizes do not depend on the storage type (fp32 partials, int32 counters): one instantiation answers

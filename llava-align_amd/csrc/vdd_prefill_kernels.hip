@@ -365,6 +365,64 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const uint16_t* __restri
     }
 }
 
+// LayerNorm with position tables (Qwen-VL ViT / resampler, experiments/Qwen_VL/visual.py:142-151,396-398):
+//   x' = round(x + pos_in[r mod T])  (pos_in optional),  y = LN(x'),  y2 = round(y + pos_out[r mod T])  (y2 only with pos_out).
+// x' is rounded to the storage type before the statistics and y before the second add: the points where the reference's
+// dtype tensors round.  The statistics are layernorm_kernel's, so y equals vdd_layernorm(vdd_add(x, pos)) bit for bit.
+__global__ void __launch_bounds__(256) layernorm_pos_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pos_in,
+                                                            const uint16_t* __restrict__ pos_out, const uint16_t* __restrict__ w,
+                                                            const uint16_t* __restrict__ b, uint16_t* __restrict__ y, uint16_t* __restrict__ y2,
+                                                            int d, int T, float eps) {
+    __shared__ float red[2][4];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const size_t off = (size_t)row * d, poff = (size_t)(row % T) * d;
+    constexpr int VPT = 2;                     // d <= 4096
+    uint4 h[VPT];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        const int e = (i * 256 + tid) * 8;
+        if (e < d) {
+            uint4 a = *reinterpret_cast<const uint4*>(x + off + e);
+            if (pos_in) {
+                const uint4 p = *reinterpret_cast<const uint4*>(pos_in + poff + e);
+                a.x = pack(lo(a.x) + lo(p.x), hi(a.x) + hi(p.x)); a.y = pack(lo(a.y) + lo(p.y), hi(a.y) + hi(p.y));
+                a.z = pack(lo(a.z) + lo(p.z), hi(a.z) + hi(p.z)); a.w = pack(lo(a.w) + lo(p.w), hi(a.w) + hi(p.w));
+            }
+            h[i] = a;
+            const float f[8] = {lo(a.x), hi(a.x), lo(a.y), hi(a.y), lo(a.z), hi(a.z), lo(a.w), hi(a.w)};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { s1 += f[k]; s2 += f[k] * f[k]; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
+    __syncthreads();
+    const float mean = (red[0][0] + red[0][1] + red[0][2] + red[0][3]) / (float)d;
+    const float var = (red[1][0] + red[1][1] + red[1][2] + red[1][3]) / (float)d - mean * mean;
+    const float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+        const int e = (i * 256 + tid) * 8;
+        if (e < d) {
+            uint4 a = h[i], gw = *reinterpret_cast<const uint4*>(w + e), gb = *reinterpret_cast<const uint4*>(b + e), o;
+            auto f = [&](uint32_t hv, uint32_t wv, uint32_t bv) {
+                return pack((lo(hv) - mean) * rstd * lo(wv) + lo(bv), (hi(hv) - mean) * rstd * hi(wv) + hi(bv));
+            };
+            o.x = f(a.x, gw.x, gb.x); o.y = f(a.y, gw.y, gb.y); o.z = f(a.z, gw.z, gb.z); o.w = f(a.w, gw.w, gb.w);
+            *reinterpret_cast<uint4*>(y + off + e) = o;
+            if (pos_out) {
+                const uint4 p = *reinterpret_cast<const uint4*>(pos_out + poff + e);
+                uint4 o2;
+                o2.x = pack(lo(o.x) + lo(p.x), hi(o.x) + hi(p.x)); o2.y = pack(lo(o.y) + lo(p.y), hi(o.y) + hi(p.y));
+                o2.z = pack(lo(o.z) + lo(p.z), hi(o.z) + hi(p.z)); o2.w = pack(lo(o.w) + lo(p.w), hi(o.w) + hi(p.w));
+                *reinterpret_cast<uint4*>(y2 + off + e) = o2;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ bias + activation
 // act: 0 none, 1 quick_gelu x*sigmoid(1.702x) (CLIP), 2 gelu erf (mlp2x_gelu projector)
 __global__ void __launch_bounds__(256) bias_act_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ bias,
@@ -561,6 +619,15 @@ VDD_HIDDEN int VDD_IMPL(vdd_layernorm)(const void* x, const void* w, const void*
     if (!x || !w || !b || !y || d % 8 != 0 || d > 4096) return VDD_ERR_INVALID_ARG;
     hipLaunchKernelGGL(layernorm_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)w,
                        (const uint16_t*)b, (uint16_t*)y, d, eps);
+    return ok();
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_layernorm_pos)(const void* x, const void* pos_in, const void* pos_out, const void* w, const void* b, void* y, void* y2,
+                                           int M, int d, int T, float eps, void* stream) {
+    if (M <= 0) return VDD_OK;
+    if (!x || !w || !b || !y || (pos_out && !y2) || d % 8 != 0 || d > 4096 || T <= 0) return VDD_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(layernorm_pos_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)pos_in,
+                       (const uint16_t*)pos_out, (const uint16_t*)w, (const uint16_t*)b, (uint16_t*)y, (uint16_t*)y2, d, T, eps);
     return ok();
 }
 

@@ -449,11 +449,12 @@ def attach_blip_engine(model, use_graph: bool = True, max_questions: int = 64):
 
 
 # ------------------------------------------------------------------ Qwen-VL (experiments/Qwen_VL/modeling_qwen.py)
-def qwen_spliced_embeddings(model, input_ids: torch.Tensor, images: Optional[torch.Tensor], feats: Optional[torch.Tensor] = None):
+def qwen_spliced_embeddings(model, input_ids: torch.Tensor, images: Optional[torch.Tensor], feats: Optional[torch.Tensor] = None, tower=None):
     """What `QWenModel.forward` feeds its decoder for a prompt with image spans (modeling_qwen.py:545-575, 631-640, 688-693): token
     embeddings with the positions between every <img> (config.visual['image_start_id']) and </img> (+1) replaced by the rows the
     CALLER'S ViT + resampler (`model.transformer.visual`: out of scope here) returns for the image - from the
-    `images` tensor when given (:565-566), else from the path spelled out in the ids (`visual.encode`, :567-568); `feats`: rows the caller already has from that tower (one [rows, d] per span).  -> list of [T, d]."""
+    `images` tensor when given (:565-566), else from the path spelled out in the ids (`visual.encode`, :567-568); `feats`: rows the caller already has from that tower (one [rows, d] per span).  tower: a qwen_visual.QwenVisualTower that replaces
+    `model.transformer.visual` (paths: the model's own `visual.image_transform` of the file, then the native tower).  -> list of [T, d]."""
     tr = model.transformer
     hidden = tr.wte(input_ids)
     start = int(model.config.visual["image_start_id"])
@@ -467,13 +468,17 @@ def qwen_spliced_embeddings(model, input_ids: torch.Tensor, images: Optional[tor
     if feats is not None:
         pass
     elif images is not None:
-        feats = tr.visual(images)
+        feats = tr.visual(images) if tower is None else tower(images)
     else:
         paths = []
         for i, a, b in pos:
             img = input_ids[i][a + 1: b - 1].tolist()
             paths.append(bytes(img[: img.index(start + 2)]).decode("utf-8"))
-        feats = tr.visual.encode(paths)
+        if tower is None:
+            feats = tr.visual.encode(paths)
+        else:
+            from PIL import Image
+            feats = tower(torch.stack([tr.visual.image_transform(Image.open(p_).convert("RGB")) for p_ in paths]))
     hidden = hidden.clone()
     for idx, (i, a, b) in enumerate(pos):
         hidden[i][a + 1: b] = feats[idx].to(hidden.dtype)
@@ -492,13 +497,14 @@ def _native_qwen_generate(model, inputs=None, generation_config=None, **kw):
     images, images_cd = kw.pop("images", None), kw.pop("images_cd", None)
     rows = _rows(input_ids, mask)
     keep = None if mask is None else torch.as_tensor(mask).to(input_ids.device).ne(0)
-    emb = qwen_spliced_embeddings(model, input_ids, images)
+    tower = getattr(model, "_vdd_tower", None)
+    emb = qwen_spliced_embeddings(model, input_ids, images, tower=tower)
     emb = emb if keep is None else [e[keep[i]] for i, e in enumerate(emb)]
     kw["inputs_embeds"] = torch.nn.utils.rnn.pad_sequence(emb, batch_first=True) if len({e.shape[0] for e in emb}) == 1 else None
     if kw["inputs_embeds"] is None:
         raise ValueError("prompts of different lengths in one call: the reference's drivers call generate() per question")
     if images_cd is not None:
-        cd = qwen_spliced_embeddings(model, input_ids, images_cd)
+        cd = qwen_spliced_embeddings(model, input_ids, images_cd, tower=tower)
         kw["images_cd"] = torch.stack(cd if keep is None else [e[keep[i]] for i, e in enumerate(cd)])
     return_dict = kw.get("return_dict_in_generate", getattr(generation_config or model.generation_config, "return_dict_in_generate", False))
     out = _native_lm_generate(model, None, generation_config, **dict(kw, return_dict_in_generate=True))
@@ -513,13 +519,17 @@ def _native_qwen_generate(model, inputs=None, generation_config=None, **kw):
     return out if return_dict else seqs
 
 
-def attach_qwen_engine(model, use_graph: bool = True, max_questions: int = 64) -> VddLlavaEngine:
+def attach_qwen_engine(model, use_graph: bool = True, max_questions: int = 64, native_visual: bool = False) -> VddLlavaEngine:
     """The native LM engine behind a `QWenLMHeadModel`-shaped object's `generate`; `model.transformer.visual` (the caller's ViT +
-    resampler) keeps producing the 256 image rows per <img> span."""
+    resampler) keeps producing the 256 image rows per <img> span - or, with native_visual, the package's qwen_visual.QwenVisualTower
+    built from that module's weights (`model._vdd_tower`) does."""
     cfg = lm_config_from_hf(model)
     eng = VddLlavaEngine(cfg, weights=lm_weights_from_hf(model, cfg), device=model.lm_head.weight.device, use_graph=use_graph,
                          max_questions=max_questions)
     model._vdd_engine = eng
+    if native_visual:
+        from .qwen_visual import QwenVisualTower, QwenVisualWeights
+        model._vdd_tower = QwenVisualTower(QwenVisualWeights.from_hf(model))
     _set_guard(model)
     model.generate = types.MethodType(_native_qwen_generate, model)
     return eng
@@ -532,6 +542,7 @@ def detach_engine(model) -> None:
     model.__dict__.pop("_vdd_engine", None)
     model.__dict__.pop("_vdd_front", None)
     model.__dict__.pop("_vdd_guard", None)
+    model.__dict__.pop("_vdd_tower", None)
     for p in model.__dict__.pop("_vdd_shared", []):
         p.data = p.data.clone(memory_format=torch.contiguous_format)
 

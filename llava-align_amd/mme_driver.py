@@ -78,6 +78,9 @@ def qwen_mme_inputs(embed_prompt: Callable[[str, Optional[str]], torch.Tensor], 
         if kind == "none":
             return {"inputs_embeds": embed_prompt("{} Answer:".format(q), None)}
         return {"inputs_embeds": embed_prompt("{} {} Answer:".format("None", q), None)}
+    hook = getattr(embed_prompt, "encode_batch", None)
+    if hook is not None:           # the native tower: a batch's distinct images in one call, before its prompts are built (run_mme)
+        build.prepare = lambda lines: hook(list(dict.fromkeys(image_path(l["image"]) for l in lines)))
     return build
 
 
@@ -142,6 +145,8 @@ def run_mme(engine: VddLlavaEngine, questions: Sequence[dict], build_inputs: Cal
             idx = mine[b0:b0 + batch_questions]
             lines = [qs_all[i] for i in idx]
             img_cache: Dict[str, dict] = {}
+            if getattr(build_inputs, "prepare", None) is not None:
+                build_inputs.prepare(lines)
 
             def main_inputs(line):
                 # one tensor object per distinct image, so that the engine shares its features and prompt-prefix KV
@@ -265,6 +270,7 @@ def main(argv=None):
     ap.add_argument("--preset", default="llava-1.5-7b")
     ap.add_argument("--vision-tower", default=None)
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16")
+    ap.add_argument("--native-visual", action="store_true", help="--arch qwen: the ViT + resampler on the package's kernels (qwen_visual)")
     a = ap.parse_args(argv)
     if a.num_beams != 1:
         raise SystemExit("num_beams > 1: the reference patches sample() only (vcd_sample.py:325-326)")
@@ -284,7 +290,7 @@ def main(argv=None):
         run_kw = dict(eos_token_id=tok.eos_token_id, pad_token_id=tok.pad_token_id or 0, stop_str="</s>", max_new_tokens=a.max_new_tokens or 128,
                       noise_step=a.noise_step if a.use_cd else None)
     else:
-        eng, tok, _model, embed_prompt = K.load_qwen(a.model_path, device, dtype=dtype)      # run_qwen.py:176-186: the ViT reads the path in the prompt
+        eng, tok, _model, embed_prompt = K.load_qwen(a.model_path, device, dtype=dtype, native_visual=a.native_visual)      # run_qwen.py:176-186: the ViT reads the path in the prompt
         build = qwen_mme_inputs(embed_prompt, lambda f: os.path.join(a.image_folder, f))
         decode = lambda ids: tok.decode(ids, skip_special_tokens=True)
         run_kw = dict(eos_token_id=tok.eod_id, pad_token_id=tok.eod_id, max_new_tokens=a.max_new_tokens or 20, min_new_tokens=1)      # run_qwen.py:194-197

@@ -29,6 +29,7 @@ _SIGS = {
     "vdd_flash_attention": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _L, _I, _F, _I, _I, _P],
     "vdd_flash_attention_packed": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _L, _I, _F, _I, _P],
     "vdd_layernorm": [_P, _P, _P, _P, _I, _I, _F, _I, _P],
+    "vdd_layernorm_pos": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P],
     "vdd_attention_probs": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _I, _L, _I, _F, _I, _P],
     "vdd_bias_act": [_P, _P, _P, _L, _I, _I, _I, _P],
     "vdd_add": [_P, _P, _P, _L, _I, _P],
@@ -1020,6 +1021,27 @@ def layernorm(x, w, b, eps, out=None):
     out = torch.empty_like(x) if out is None else out
     _lib.check(_lib_ready().vdd_layernorm(x.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), M, d, eps, dt, _st(x)))
     return out
+
+
+
+def layernorm_pos(x, w, b, eps, pos_in=None, pos_out=None, out=None, out2=None):
+    """y = LN(x + pos_in[r mod T]) with x + pos_in rounded to the storage type first; with pos_out also y2 = y + pos_out[r mod T]
+    (rounded).  pos tables [T, d], T = their row count.  Returns y, or (y, y2) with pos_out."""
+    dt = _dt(x, w, b, pos_in, pos_out)
+    M, d = x.shape
+    T = (pos_in if pos_in is not None else pos_out).shape[0] if (pos_in is not None or pos_out is not None) else 1
+    for p_ in (pos_in, pos_out):
+        if p_ is not None and (p_.shape != (T, d) or not p_.is_contiguous()):
+            raise ValueError(f"layernorm_pos: position tables must be contiguous [T, {d}] of one T")
+    if not x.is_contiguous():
+        raise ValueError("layernorm_pos: x must be contiguous")
+    out = torch.empty_like(x) if out is None else out
+    if pos_out is not None:
+        out2 = torch.empty_like(x) if out2 is None else out2
+    _lib.check(_lib_ready().vdd_layernorm_pos(x.data_ptr(), pos_in.data_ptr() if pos_in is not None else None,
+                                              pos_out.data_ptr() if pos_out is not None else None, w.data_ptr(), b.data_ptr(), out.data_ptr(),
+                                              out2.data_ptr() if pos_out is not None else None, M, d, T, eps, dt, _st(x)))
+    return (out, out2) if pos_out is not None else out
 
 
 ACT_NONE, ACT_QUICK_GELU, ACT_GELU = 0, 1, 2

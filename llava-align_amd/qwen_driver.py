@@ -13,8 +13,10 @@ min_new_tokens=1, pad = eos = tokenizer.eod_id, temperature, top_p, top_k, ...)`
 Only the step-0 scores of the four prior passes are used (:66-68), so they decode ONE token here.  Each pass is one engine call
 over a whole batch of questions.
 
-The Qwen ViT + resampler are outside the north-star path: `embed_prompt(text, image) -> [T, d]` is the
-caller's front-end - token embeddings with the 256 slots between <img> and </img> filled from `image` (a [3, S, S] tensor: what the
+`embed_prompt(text, image) -> [T, d]` is the
+caller's front-end (checkpoint.qwen_embed_prompt: the model's own ViT + resampler, or with --native-visual the package's
+qwen_visual.QwenVisualTower, whose `encode_batch` runs a batch's distinct images - and under --use_cd its per-question noised copies - in
+one tower call) - token embeddings with the 256 slots between <img> and </img> filled from `image` (a [3, S, S] tensor: what the
 reference passes as `images=`, modeling_qwen.py:565-566) or, for prompts without an image span, image = None.  It may return
 `(embeddings, n_shared)`, n_shared = the leading rows every prompt about the same image tensor starts with ('<img>' + the slots).
 """
@@ -39,7 +41,12 @@ def _unwrap(e):
 
 
 def _embeds(embed_prompt, texts, images, keys):
-    """-> (list of [T, d], embeds_prefix list or None).  keys[i]: what identifies images[i] (rows with one key share the image span's K/V)."""
+    """-> (list of [T, d], embeds_prefix list or None).  keys[i]: what identifies images[i] (rows with one key share the image span's K/V).
+    An embed_prompt with `encode_batch` (checkpoint.qwen_embed_prompt over the native tower) gets the call's distinct images in ONE tower
+    call first; the prompts then find their rows kept."""
+    hook = getattr(embed_prompt, "encode_batch", None)
+    if hook is not None:
+        hook(list({id(im): im for im in images if im is not None}.values()))
     out, pre = [], []
     for t, im, k in zip(texts, images, keys):
         e, n = _unwrap(embed_prompt(t, im))
@@ -243,11 +250,12 @@ def main(argv=None):
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="bfloat16")
+    ap.add_argument("--native-visual", action="store_true", help="the ViT + resampler on the package's kernels (qwen_visual) instead of the model's module")
     a = ap.parse_args(argv)
     from . import checkpoint as K
     from .shard import get_chunk, init_from_env
     rank, world, device = init_from_env()
-    eng, tok, model, embed_prompt = K.load_qwen(a.model_path, device, dtype=getattr(torch, a.dtype))
+    eng, tok, model, embed_prompt = K.load_qwen(a.model_path, device, dtype=getattr(torch, a.dtype), native_visual=a.native_visual)
     questions = [json.loads(q) for q in open(os.path.expanduser(a.question_file))]
     if a.num_chunks > 1:
         questions = [questions[i] for i in get_chunk(len(questions), a.num_chunks, a.chunk_idx, group=1)]
