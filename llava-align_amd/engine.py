@@ -685,6 +685,28 @@ class StepAttentions:
         raise IndexError(f"attentions[{i}]: only step 0 is materialised (llava_calibrate.py:180 reads ['attentions'][0][-1])")
 
 
+def branch_names(use_cd: bool, use_dd: bool, use_dd_unk: bool) -> List[str]:
+    """The branches of a call, in row order (vcd_sample.py:147-177): the VCD branch takes the place of the first image-free one
+    (:148-150); use_dd_unk adds `unk` (:154-155), use_dd alone `none` (:157-160), and both together `unk` + `none` (:171-177)."""
+    second = "cd" if use_cd else "unk" if use_dd_unk else "none" if use_dd else None
+    return ["main"] + ([second] if second else []) + (["none"] if use_dd and use_dd_unk else [])
+
+
+def branch_rows(name: str, ids_list: List[list]) -> List[list]:
+    """A branch's prompt ids from the main ids: `unk` turns the image slot into token 0 (<unk>), `none` drops it; main / cd: the list itself."""
+    if name == "unk":
+        return [[0 if t == IMAGE_TOKEN_INDEX else t for t in r] for r in ids_list]
+    if name == "none":
+        return [[t for t in r if t != IMAGE_TOKEN_INDEX] for r in ids_list]
+    return ids_list
+
+
+def slot_cut(name: str, ids: list, s_img: int):
+    """(prefix, suffix) tokens of branch `name` around the image slot s_img of the MAIN ids: the suffix follows the slot, `unk` keeps its
+    <unk> token in the prefix (quirk #3); main / cd put the image rows between the two."""
+    return ids[:s_img] + ([0] if name == "unk" else []), ids[s_img + 1:]
+
+
 def group_rows_by_prefix(rows):
     """rows: [[slot, len, pslot, plen], ...] -> (groups [[row_off, n_rows, pslot, plen]], flat member row ids);
     rows without a prefix belong to no group."""
@@ -813,19 +835,12 @@ class _DecodeRunner:
         self.step_idx.fill_(1)
         self.ctr += 1
 
-    def adopt(self, old: "_DecodeRunner", q_idx: torch.Tensor, n_new: int):
-        """Continue `old`'s decoding with the questions q_idx (int64 device tensor, ascending) only: their rows (branch-major in both
-        runners) take the slots 0 .. len - 1 of the repacked own pools, in row order.  Device -> device, no sync."""
-        Qo, Qn, nb = old.Q, self.Q, self.nb
-        rows_idx = torch.cat([q_idx + b * Qo for b in range(nb)])
-        self.pos.copy_(old.pos[rows_idx]); self.cpos.copy_(old.cpos[rows_idx])
-        self.rows.copy_(old.rows[rows_idx])
-        new_slot = torch.arange(nb * Qn, dtype=torch.int32, device=self.pos.device)
-        self.slot.copy_(new_slot)
-        self.rows[:, 0] = new_slot
-        self.tok.copy_(old.tok[q_idx])
-        self.unfinished.copy_(old.unfinished[q_idx])
-        self.gen[:, :n_new] = old.gen[q_idx, :n_new]
+    def _take(self, old: "_DecodeRunner", q_idx: torch.Tensor) -> torch.Tensor:
+        """All state but `slot` / `gen` of `old`'s questions q_idx (int64 device tensor, ascending) and their rows (branch-major in both
+        runners), device -> device, no sync.  Returns the old row indices."""
+        rows_idx = torch.cat([q_idx + b * old.Q for b in range(self.nb)])
+        self.pos.copy_(old.pos[rows_idx]); self.cpos.copy_(old.cpos[rows_idx]); self.rows.copy_(old.rows[rows_idx])
+        self.tok.copy_(old.tok[q_idx]); self.unfinished.copy_(old.unfinished[q_idx])
         self.step_idx.copy_(old.step_idx); self.ctr.copy_(old.ctr)
         self.status.copy_(old.status[q_idx]); self.status0.copy_(old.status0[q_idx])
         # the processor stage's per-question state (EOS floor, stop-word prompt tails, repetition-penalty history) moves with its question
@@ -836,7 +851,17 @@ class _DecodeRunner:
         if self.prompt_ids is not None:
             self.prompt_ids.copy_(old.prompt_ids[q_idx])
             self.prompt_cols = old.prompt_cols
-        return old.slot[rows_idx].long()                           # the old slots of the kept rows, in the new slot order
+        return rows_idx
+
+    def adopt(self, old: "_DecodeRunner", q_idx: torch.Tensor, n_new: int):
+        """Continue `old`'s decoding with the questions q_idx only: their rows take the slots 0 .. len - 1 of the repacked own pools, in
+        row order.  Returns the old slots of the kept rows, in the new slot order."""
+        rows_idx = self._take(old, q_idx)
+        new_slot = torch.arange(self.nb * self.Q, dtype=torch.int32, device=self.pos.device)
+        self.slot.copy_(new_slot)
+        self.rows[:, 0] = new_slot
+        self.gen[:, :n_new] = old.gen[q_idx, :n_new]
+        return old.slot[rows_idx].long()
 
     def admit(self, q_idx: torch.Tensor, tok, unfinished, status0, pos, cpos, rows, pad: int):
         """Admission mode: the question slots q_idx (int64 device tensor) start NEW questions whose first token `tok` was just sampled from
@@ -858,12 +883,19 @@ class _DecodeRunner:
     def adopt_slots(self, old: "_DecodeRunner", q_idx: torch.Tensor):
         """Admission mode, tail of a list: continue `old`'s decoding with its question slots q_idx only.  Own-KV slots are addressed per row
         (`slot`), so nothing moves in the pools - the smaller step just lists the surviving rows."""
-        Qo, nb = old.Q, self.nb
-        rows_idx = torch.cat([q_idx + b * Qo for b in range(nb)])
-        self.pos.copy_(old.pos[rows_idx]); self.cpos.copy_(old.cpos[rows_idx]); self.slot.copy_(old.slot[rows_idx]); self.rows.copy_(old.rows[rows_idx])
-        self.tok.copy_(old.tok[q_idx]); self.unfinished.copy_(old.unfinished[q_idx]); self.gen.copy_(old.gen[q_idx]); self.s0.copy_(old.s0[q_idx])
-        self.step_idx.copy_(old.step_idx); self.ctr.copy_(old.ctr)
-        self.status.copy_(old.status[q_idx]); self.status0.copy_(old.status0[q_idx])
+        rows_idx = self._take(old, q_idx)
+        self.slot.copy_(old.slot[rows_idx]); self.gen.copy_(old.gen[q_idx]); self.s0.copy_(old.s0[q_idx])
+
+    def failed(self) -> torch.Tensor:                           # device bool: a row lost every finite score
+        return (self.status | self.status0).ne(0).any()
+
+    def poll(self):                                             # ONE sync: (unfinished flag per question, failed)
+        state = torch.cat([self.unfinished, self.failed().long()[None]]).tolist()
+        return state[:-1], state[-1]
+
+    def raise_if_failed(self):
+        if bool(self.failed().item()):
+            raise RuntimeError("probability tensor contains either `inf`, `nan` or element < 0")   # torch.multinomial, vcd_sample.py:202
 
     def body(self, kv):
         t, Q, nb = self.tail, self.Q, self.nb
@@ -883,6 +915,7 @@ class _DecodeRunner:
         else:
             self.sample_tail(v, c, d, self.scores_buf, False, status_out=self._st, step_ptr=self.step_idx)
         self.status |= self._st
+        dead = None
         if self.s0 is None:
             self.gen.index_copy_(1, self.step_idx, self.tok[:, None])
             self.pos += 1
@@ -893,8 +926,6 @@ class _DecodeRunner:
                 # rows stop attending their context - ONE key - until the batch ends or they are retired (K / V bytes of a step follow the
                 # LIVE rows; the grouped pass keeps its group tables, and per-step score rows stay the reference's)
                 dead = (self.unfinished == 0).repeat(nb)
-                self.rows[:, 1].masked_fill_(dead, 1)
-                self.rows[:, 3].masked_fill_(dead, 0)
         else:
             # per-slot column; a slot whose answer reached max_new tokens is finished like one that emitted EOS; finished slots (pad tokens
             # from the kernel) write the slack column and do not move: they rewrite ONE KV position and attend a fixed context until a
@@ -909,6 +940,7 @@ class _DecodeRunner:
             # ... and stop attending their context: a finished row reads ONE key until its slot is taken (a third of the K / V bytes of a
             # step were those of finished rows near the end of a list)
             dead = alive == 0
+        if dead is not None:
             self.rows[:, 1].masked_fill_(dead, 1)
             self.rows[:, 3].masked_fill_(dead, 0)
         self.step_idx += 1
@@ -1003,8 +1035,7 @@ class VddLlavaEngine:
         cur = self._kvs.get(frag_only)
         if cur is None or not cur.fits(n_pre, t_pre, n_own, t_own, frag_only):
             self._kvs.pop(frag_only, None)
-            for k in [k for k, r in self._graphs.items() if r.kv is cur]:     # captured steps point into the pools being replaced
-                self._graphs.pop(k)
+            self._drop_graphs(cur)
             grow = lambda a, b: max(a, b)
             if cur is not None:
                 n_pre, t_pre, n_own, t_own = grow(n_pre, cur.n_pre), grow(t_pre, cur.t_pre), grow(n_own, cur.n_own), grow(t_own, cur.t_own)
@@ -1017,8 +1048,7 @@ class VddLlavaEngine:
                 free, _total = torch.cuda.mem_get_info(self.device)
                 if need > free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device):
                     # both forms do not fit side by side: the other one (and its graphs) goes
-                    for k in [k for k, r in self._graphs.items() if r.kv is other]:
-                        self._graphs.pop(k)
+                    self._drop_graphs(other)
                     self._kvs.pop(not frag_only)
                     if self._kv is other:
                         self._kv = None
@@ -1172,14 +1202,11 @@ class VddLlavaEngine:
             # its ids never contain IMAGE_TOKEN_INDEX, vcd_sample.py:154-160 change nothing): the image-free branches re-run the
             # SAME inputs on their own KV caches, c ~ v, and the contrast reduces to the beta-mask.  Reproduced as such: the extra
             # branches get the main branch's embeddings (the dual / triple forward pass is really executed).
-            emb_main = [e.reshape(-1, lm.d) for e in (inputs_embeds if not torch.is_tensor(inputs_embeds) else list(inputs_embeds))]
-            emb_cd = None
-            if images_cd is not None:
-                emb_cd = [e.reshape(-1, lm.d) for e in (images_cd if not torch.is_tensor(images_cd) else list(images_cd))]
+            emb_main = [e.reshape(-1, lm.d) for e in inputs_embeds]
+            emb_cd = [e.reshape(-1, lm.d) for e in images_cd] if images_cd is not None else None
             input_ids = [torch.zeros(0, dtype=torch.long) for _ in emb_main]
             images = None
-        ids_list = [r for r in input_ids] if torch.is_tensor(input_ids) else list(input_ids)
-        ids_list = [r.reshape(-1).tolist() for r in ids_list]
+        ids_list = [r.reshape(-1).tolist() for r in input_ids]
         Q = len(ids_list)
         prompt_lens = [0] * Q if inputs_embeds is not None else [len(r) for r in ids_list]     # HF's input_ids length per row
         if max_length is not None:
@@ -1190,22 +1217,10 @@ class VddLlavaEngine:
                 raise ValueError(f"max_length {max_length} leaves no room behind a prompt of {prompt_lens[0]} tokens")
         # the vision tower needs nothing of the planning below: its launches go out first, so the host-side validation / planning
         # of ~800 prompts (20-30 ms of Python) runs under its GPU time instead of in front of it
-        # reuse_prefill: a sweep over sampling settings (the reference's scripts run 51 of them over the same questions, MME/run_llava.py:281-318)
-        # asks for the SAME prompts again - only the warpers / seed / alpha / beta differ, and none of them enters the prefill.  The call keeps
-        # its plan, pools and step-0 logits; the next reuse_prefill call with the same prompt and image tensors (the caller's promise: unchanged),
-        # the same branches and no more new tokens skips the vision tower and the prefill and decodes again from that state (a decode only writes
-        # own-KV positions behind the prompt).  Not with the VCD branch (fresh noise per call); such calls never retire rows.
         hit, rkey = None, None
-        if reuse_prefill and not output_attentions:
-            eff = (False, False) if not do_sample else (bool(use_dd), bool(use_dd_unk))
-            if images_cd is None or not do_sample:
-                ims = None if images is None else tuple((images[i].data_ptr(), tuple(images[i].shape)) for i in range(Q))
-                embs = None if inputs_embeds is None else tuple((e.data_ptr(), tuple(e.shape)) for e in emb_main)
-                rkey = (tuple(map(tuple, ids_list)), ims, embs, tuple(embeds_prefix) if embeds_prefix is not None else None, eff, share_prefix,
-                        self.two_level_prefix, self.share_repeated_rows, self.group_attention, ops.GEMM_BATCH_INVARIANT, str(self.dtype))
-                c_ = self._prefill_cache
-                if c_ is not None and c_["key"] == rkey and self._kvs.get(c_["frag"]) is c_["kv"] and max_new_tokens <= c_["max_new"]:
-                    hit = c_
+        if reuse_prefill and not output_attentions and (images_cd is None or not do_sample):
+            hit, rkey = self._reuse_lookup(ids_list, images, emb_main if inputs_embeds is not None else None, embeds_prefix,
+                                           (bool(use_dd), bool(use_dd_unk)) if do_sample else (False, False), share_prefix, max_new_tokens)
         feats = None
         if images is not None and hit is None:
             imgs = [images[i] for i in range(Q)] if torch.is_tensor(images) else list(images)
@@ -1234,43 +1249,18 @@ class VddLlavaEngine:
         proc, proc_key = self._processor_config(prompt_lens, ids_list, eos_token_id, min_new_tokens, min_length, stop_words_ids,
                                                 repetition_penalty, logits_processor, max_new_tokens)
 
-        # ---- branches: (name, per-question token lists with image slot handling) ------------
-        feats_cd = None
-        if use_cd and inputs_embeds is None:
-            imgs_cd = [images_cd[i] for i in range(Q)] if torch.is_tensor(images_cd) else list(images_cd)
-            # the noised copies differ per question (fresh noise, llava_calibrate.py:152-155): no feature cache, but full tower chunks
-            # instead of one launch chain per question
-            feats_cd = []
-            for i0 in range(0, Q, self.VIT_CHUNK):
-                chunk = [im.reshape(im.shape[-3:]).to(dev) for im in imgs_cd[i0:i0 + self.VIT_CHUNK]]
-                feats_cd += list(self.vit(torch.stack(chunk)))
+        # ---- branches: (name, per-question ids, per-question image features / prompt embeddings) ------------
+        names = branch_names(use_cd, use_dd, use_dd_unk)
         if hit is not None:
             branches = hit["branches"]
         elif inputs_embeds is not None:
+            # the image-free branches get the main branch's list ITSELF: _plan shares their prefixes by identity
             main_dev = [e.to(dev, self.dtype) for e in emb_main]
-            branches = [("main", ids_list, main_dev)]
-            if use_cd:
-                branches.append(("cd", ids_list, [e.to(dev, self.dtype) for e in emb_cd]))
-            elif use_dd_unk:
-                branches.append(("unk", ids_list, main_dev))
-            elif use_dd:
-                branches.append(("none", ids_list, main_dev))
-            if use_dd and use_dd_unk:
-                branches.append(("none", ids_list, main_dev))
+            cd_dev = [e.to(dev, self.dtype) for e in emb_cd] if use_cd else None
+            branches = [(nm, ids_list, cd_dev if nm == "cd" else main_dev) for nm in names]
         else:
-            branches = [("main", ids_list, feats)]
-        if hit is not None:
-            pass
-        elif use_cd and inputs_embeds is None:
-            branches.append(("cd", ids_list, feats_cd))                                       # :148-150, takes precedence
-        elif inputs_embeds is not None:
-            pass
-        elif use_dd_unk:
-            branches.append(("unk", [[0 if t == IMAGE_TOKEN_INDEX else t for t in r] for r in ids_list], None))   # :154-155
-        elif use_dd:
-            branches.append(("none", [[t for t in r if t != IMAGE_TOKEN_INDEX] for r in ids_list], None))         # :157-160
-        if use_dd and use_dd_unk and inputs_embeds is None and hit is None:
-            branches.append(("none", [[t for t in r if t != IMAGE_TOKEN_INDEX] for r in ids_list], None))         # :171-177
+            feats_cd = self._noised_features([images_cd[i] for i in range(Q)]) if use_cd else None
+            branches = [(nm, branch_rows(nm, ids_list), {"main": feats, "cd": feats_cd}.get(nm)) for nm in names]
         nb = len(branches)
 
         # ---- plan prefill: split every (branch, question) sequence into shared prefix + own suffix -----
@@ -1308,8 +1298,8 @@ class VddLlavaEngine:
                      suffix_max + own_cap, frag_only=bool(grp))
         if hit is not None and (kv is not hit["kv"] or bool(grp) != hit["frag"]):
             raise RuntimeError("reuse_prefill: the pools of the kept prefill were replaced")       # (cannot happen: same plan, no more new tokens)
-        if hit is None and self._prefill_cache is not None and self._prefill_cache["kv"] is kv:
-            self._prefill_cache = None                         # this call's prefill overwrites the pools the kept state lives in
+        if hit is None:
+            self._forget_kept_prefill(kv)
         if plan["max_len"] + max_new_tokens > self.cfg.lm.max_pos:
             raise ValueError(f"prompt ({plan['max_len']} positions) + max_new_tokens ({max_new_tokens}) exceed the rotary table "
                              f"(max_pos = {self.cfg.lm.max_pos}): lower max_new_tokens or build the engine with a larger LMConfig.max_pos")
@@ -1325,61 +1315,29 @@ class VddLlavaEngine:
         if hit is not None:
             logits0 = hit["logits0"]
         else:
-            if plan["prefix"]:
-                # level 0: the prefixes that continue nothing; level 1: image prefixes behind a shared system prompt (their pass runs second in
-                # every layer: it attends the parent's K / V of that layer, and copies them in front of its own rows)
-                for level in (0, 1):
-                    segs = [s_ for s_ in plan["prefix"] if (s_.get("cpos0", 0) > 0) == bool(level)]
-                    if not segs:
-                        continue
-                    x, pos, cpos, slot, seqs, max_tq = self._pack(segs)
-                    pd = dict(x=x, pos=pos, cpos=cpos, slot=slot, seqs=seqs, n_seq=len(segs), max_tq=max_tq, to_prefix_pool=True, keep_q=want_maps)   # K/V only
-                    if level:
-                        n_sys = segs[0]["cpos0"]
-                        pd.update(own_row_offset=n_sys, parent_copy=(h2d_long(dev, [s_["slot"] for s_ in segs]),
-                                                                       segs[0]["pslot"], n_sys))
-                    passes.append(pd)
-                if kv.frag_only:
-                    (frag_plen,) = h2d_int32(dev, [s_.get("full_T", s_["T"]) for s_ in plan["prefix"]])
-            segs = plan["suffix"]
-            x, pos, cpos, slot, seqs, max_tq = self._pack(segs)
-            # short suffixes behind shared prefixes: four sequences of one prefix per attention workgroup (ops.flash_packs)
-            packs_h = ops.flash_packs([[0, 0, 0, 0, s["pslot"], s["plen"]] for s in segs]) if (max_tq <= 32 and lm.head_dim == 128 and (not ops.GEMM_BATCH_INVARIANT or ops.FLASH_PACKS_IN_INVARIANT_MODE)) else None
-            last, last_seqs, packs = h2d_int32(dev, [s["q_row0"] + s["T"] - 1 for s in segs],
-                                               [[i, 1, s["pos0"] + s["T"] - 1, s["slot"], s["pslot"], s["plen"]] for i, s in enumerate(segs)],
-                                               packs_h if packs_h is not None else [[0, -1, -1, -1]])
-            passes.append(dict(x=x, pos=pos, cpos=cpos, slot=slot, seqs=seqs, n_seq=len(segs), max_tq=max_tq, to_prefix_pool=False,
-                               last_rows=last.long(), last_seqs=last_seqs, packs=packs if packs_h is not None else None, keep_q=want_maps))
+            # level 0: the prefixes that continue nothing; level 1: image prefixes behind a shared system prompt (their pass runs second in
+            # every layer: it attends the parent's K / V of that layer, and copies them in front of its own rows)
+            for level in (0, 1):
+                segs = [s_ for s_ in plan["prefix"] if (s_.get("cpos0", 0) > 0) == bool(level)]
+                if not segs:
+                    continue
+                pd = self._prefill_pass(segs, to_prefix_pool=True, keep_q=want_maps)                 # K/V only
+                if level:
+                    n_sys = segs[0]["cpos0"]
+                    pd.update(own_row_offset=n_sys, parent_copy=(h2d_long(dev, [s_["slot"] for s_ in segs]), segs[0]["pslot"], n_sys))
+                passes.append(pd)
+            if plan["prefix"] and kv.frag_only:
+                (frag_plen,) = h2d_int32(dev, [s_.get("full_T", s_["T"]) for s_ in plan["prefix"]])
+            passes.append(self._prefill_pass(plan["suffix"], to_prefix_pool=False, last=True, packs=True, keep_q=want_maps))
             resid, delta = self.lm.prefill(passes, kv, frag_plen=frag_plen)[-1]
             logits0 = self.lm.logits(resid, delta)                                        # [nb*Q, V], rows ordered branch-major
             if rkey is not None:
-                self._prefill_cache = dict(key=rkey, kv=kv, frag=bool(grp), plan=plan, branches=branches, logits0=logits0, max_new=max_new_tokens)
+                self._reuse_store(rkey, kv, bool(grp), plan, branches, logits0, max_new_tokens)
         self.debug_logits0 = logits0
-        attn_maps = None
-        if want_maps:
-            # question 0, main branch = suffix sequence 0 (+ its prefix slot): [prefix rows | suffix rows] of the last layer's rotated queries
-            s0 = plan["suffix"][0]
-            q_rows = [passes[-1]["q_last"][s0["q_row0"]: s0["q_row0"] + s0["T"]]]
-            if s0["plen"] > 0:
-                p0 = plan["prefix"][s0["pslot"]]
-                q_rows.insert(0, passes[0]["q_last"][p0["q_row0"]: p0["q_row0"] + p0["T"]])
-            q_full = torch.cat(q_rows, 0) if len(q_rows) > 1 else q_rows[0].contiguous()
-            li = lm.n_layers - 1
-            m = ops.attention_probs(q_full, kv.ko[li], (0, q_full.shape[0], 0, s0["slot"], s0["pslot"], s0["plen"]), lm.n_heads, lm.n_kv_heads,
-                                    lm.head_dim, k_prefix=kv.kp[li])
-            attn_maps = m[None]                                                      # [1, H, T, T] like HF's attention weights
-            for p_ in passes:
-                p_.pop("q_last", None)
-        V = lm.vocab
+        attn_maps = self._attention_map(plan, passes, kv) if want_maps else None
 
         # ---- step 0: sample from the prefill logits (eager; also yields the top-n for calibration) -----------
-        # device-side Philox counter = (stream, step): graphs are seed-agnostic.  seed=None: the stream id is drawn from torch's
-        # default generator, so every generate() call samples fresh numbers (the reference's torch.multinomial advances the
-        # generator too) and torch.manual_seed() reproduces a run's random numbers; an explicit seed is a pure function of the seed.
-        # (The bf16 logits they are applied to depend, in their last bits, on the GEMM schedule the tuner picked: ops.gemm_choices_export.)
-        from .sampling import fresh_offset
-        sd = (fresh_offset() if seed is None else int(seed)) & 0x3FFFFFFFFF
-        ctr0 = sd << 24
+        ctr0 = self._philox_counter(seed)
         eos_t = h2d_long(dev, eos_token_id) if eos_token_id is not None else None
         cfgkey = (Q, nb, max_new_tokens, alpha, beta, warp.t, warp.k, warp.p, use_cd, use_dd, use_dd_unk, cd_greedy,
                   tuple(eos_token_id) if eos_token_id is not None else None, pad_token_id, output_scores, ops.GEMM_BATCH_INVARIANT)
@@ -1426,23 +1384,13 @@ class VddLlavaEngine:
             if inputs_embeds is None:
                 streamer.put(torch.tensor([ids_list[0]], dtype=torch.long))
             streamer.put(run.gen[:, 0].cpu())
-        # The host runs ahead of the device (a captured step is one graph launch): without an EOS check nothing ever waits, and a 256-token
-        # generation used to leave > 100,000 kernel packets queued at once.  The HIP runtime copes (it blocks on a full queue), a tool
-        # intercepting the queue does not: rocprofv3 aborted the process / segfaulted at a deterministic dispatch index once ~30 - 60
-        # thousand packets were outstanding (tools/rocprof_abort_bisect.py: 64 new tokens fine, 128 x 2 and 256 not, eager fine).
-        # So the loop waits for the step launched LAUNCH_WINDOW steps ago before going on: at most 2 x 16 steps in flight, no measurable cost.
         marks = []
         while n_new < max_new_tokens:
             run.step(kv)
             if output_scores:
                 scores.append(run.scores_buf.clone())
             n_new += 1
-            if n_new % self.LAUNCH_WINDOW == 0:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                marks.append(ev)
-                if len(marks) > 1:
-                    marks.pop(0).synchronize()
+            self._throttle(n_new, marks)
             if streamer is not None:
                 streamer.put(run.gen[:, n_new - 1].cpu())
                 if eos_t is not None and int(run.unfinished.max().item()) == 0:
@@ -1451,8 +1399,7 @@ class VddLlavaEngine:
             # are 1-2 tokens: waiting for step 8 would run six decode steps for nobody)
             if eos_t is not None and (n_new % sync_every == 0 or n_new == max_new_tokens or (n_new in (2, 4) and n_new < sync_every)):
                 if retire:
-                    state = torch.cat([run.unfinished, (run.status | run.status0).ne(0).any().long()[None]]).tolist()    # ONE sync
-                    unf, bad = state[:-1], state[-1]
+                    unf, bad = run.poll()
                     if bad or not any(unf):
                         break
                     live_q = [j for j, u in enumerate(unf) if u]
@@ -1463,51 +1410,36 @@ class VddLlavaEngine:
                         live_q = list(range(len(unf)))                                  # growth only: everybody stays
                     if n_new < max_new_tokens and (grow or shrink):
                         # finished questions leave: their tokens go to `master`, the live rows move to the front of new own pools
-                        idx_all = torch.tensor(alive, dtype=torch.long, device=dev)
-                        master[idx_all, :n_new] = run.gen[:, :n_new]
-                        q_idx = torch.tensor(live_q, dtype=torch.long, device=dev)
+                        master[torch.tensor(alive, dtype=torch.long, device=dev), :n_new] = run.gen[:, :n_new]
                         cap = kv.t_own - suffix_max
                         if grow:
                             cap = min(max_new_tokens, max(cap + cap // 2, n_new + 2 * sync_every + 2))
-                        Qn = len(live_q)
-                        self._graphs = {k_: r_ for k_, r_ in self._graphs.items() if r_.kv is not kv}    # captured steps point into the old pools
-                        new_run = _DecodeRunner(self, Qn, run.nb, max_new_tokens, dict(run.tail), kv)
-                        old_slots = new_run.adopt(run, q_idx, n_new)
-                        kv.repack_own(old_slots, own_len, suffix_max + cap)
-                        new_run.workspace = ops.attention_workspace(run.nb * Qn, lm.n_heads, lm.head_dim, kv.t_pre + (kv.t_own + 63) // 64 * 64, dev)
-                        for k_ in [k_ for k_ in self._graphs if len(k_) > len(cfgkey) and k_[len(cfgkey)] == "retired"]:
-                            self._graphs.pop(k_)                          # the runner of the previous retirement event: nothing replays it again
-                        self._graphs[cfgkey + ("retired", Qn, kv.t_own, stats["retire_events"])] = new_run
+                        run = self._retire_rows(run, live_q, n_new, own_len, suffix_max + cap, cfgkey, stats["retire_events"])
                         alive = [alive[j] for j in live_q]
-                        run = new_run
                         stats["retire_events"] += 1
-                        stats.setdefault("retire_log", []).append((n_new, run.nb * Qn, cap))
-                        stats["rows_at_end"], stats["own_capacity"] = run.nb * Qn, cap
+                        stats.setdefault("retire_log", []).append((n_new, run.nb * run.Q, cap))
+                        stats["rows_at_end"], stats["own_capacity"] = run.nb * run.Q, cap
                     continue
-                done_bad = torch.stack([run.unfinished.max() == 0, (run.status | run.status0).ne(0).any()]).tolist()   # ONE sync
-                if done_bad[1]:                                 # a row lost every finite score: stop decoding from token -1
-                    break
-                if done_bad[0]:                                                               # :291, amortised over sync_every steps
+                # ONE sync: everybody finished (:291, amortised over sync_every steps), or a row lost every finite score (stop decoding from token -1)
+                if any(torch.stack([run.unfinished.max() == 0, run.failed()]).tolist()):
                     break
         if events is not None:
             events[2].record(torch.cuda.current_stream(dev))
             stats["events"], stats["steps_run"] = events, n_new
             self.call_log.append(stats)
-        if bool((run.status | run.status0).ne(0).any().item()):
-            raise RuntimeError("probability tensor contains either `inf`, `nan` or element < 0")   # torch.multinomial, :202
+        run.raise_if_failed()
         if streamer is not None:
             streamer.end()
         if retire:
             master[torch.tensor(alive, dtype=torch.long, device=dev), :n_new] = run.gen[:, :n_new]
             gen = master[:, :n_new].clone()
             if run.Q != Q:                                     # the pools (and the last runner) are those of the survivors only
-                self._graphs = {k_: r_ for k_, r_ in self._graphs.items() if r_.kv is not kv}
-            for k_ in [k_ for k_ in self._graphs if len(k_) > len(cfgkey) and k_[len(cfgkey)] == "retired"]:
-                self._graphs.pop(k_)                           # a grown-only runner: its pools are sized for this call's tail, not the next call's start
+                self._drop_graphs(kv)
+            self._drop_retired_runner(cfgkey)                  # a grown-only runner: its pools are sized for this call's tail, not the next call's start
         else:
             gen = run.gen[:, :n_new].clone()
         if eos_t is not None:
-            gen = self._trim_after_all_finished(gen, eos_t, pad_token_id)
+            gen, _ = self._trim_after_all_finished(gen, eos_t)
             if scores is not None:
                 scores = scores[:gen.shape[1]]
         # prompt ids back on the device in ONE copy (a torch.tensor(..., device=) per question is a synchronous pageable copy each)
@@ -1575,10 +1507,8 @@ class VddLlavaEngine:
         vcd = images_cd is not None
         if vcd and len(images_cd) != N:
             raise ValueError("generate_list: one images_cd entry per question")
-        if vcd:                                                  # vcd_sample.py:148-150: the cd branch takes the place of the first image-free branch
-            names = ["main"] + (["none"] if (use_dd and use_dd_unk) else [])
-        else:
-            names = ["main"] + (["unk"] if use_dd_unk else (["none"] if use_dd else [])) + (["none"] if (use_dd and use_dd_unk) else [])
+        # the cd branch contrasts step 0 only: it is prefilled at admission into scratch prefix slots and never decodes
+        names = [nm for nm in branch_names(vcd, use_dd, use_dd_unk) if nm != "cd"]
         nb, contrast = len(names), vcd or len(names) > 1
         alpha = cd_alpha if cd_alpha is not None else 0.5
         beta = cd_beta if cd_beta is not None else 0.1
@@ -1622,17 +1552,15 @@ class VddLlavaEngine:
         admit_min = min(admit_min, max(1, Qc // 2))
         n_pre = pre_slots(Qc)
         kv = self.kv(n_pre, t_pool, nb * Qc, suffix_cap + max_new_tokens, frag_only=False)
-        if self._prefill_cache is not None and self._prefill_cache["kv"] is kv:
-            self._prefill_cache = None                           # (generate(reuse_prefill=True): its kept state lives in these pools)
+        self._forget_kept_prefill(kv)
         eos_t = h2d_long(dev, eos_token_id)
-        from .sampling import fresh_offset
-        sd = (fresh_offset() if seed is None else int(seed)) & 0x3FFFFFFFFF
+        ctr0 = self._philox_counter(seed)
         cfgkey = ("list", Qc, nb, max_new_tokens, alpha, beta, warp.t, warp.k, warp.p, use_dd, use_dd_unk, vcd, cd_greedy, tuple(eos_token_id), pad_token_id,
                   ops.GEMM_BATCH_INVARIANT)
         tail = dict(alpha=alpha, beta=beta, warp=warp, contrast=contrast, is_vcd=vcd, both=(use_dd and use_dd_unk), greedy=cd_greedy, eos_t=eos_t,
                     pad=pad_token_id, output_scores=False, n_groups=0, n_items=0, cpi=1, proc={}, admit=True)
         run = self._runner(cfgkey, Qc, nb, max_new_tokens, tail, kv)
-        run.reset(sd << 24)
+        run.reset(ctr0)
         run.unfinished.zero_()                                   # every slot starts free
         run.slot.copy_(torch.arange(nb * Qc, dtype=torch.int32, device=dev))
         # a free slot decodes a harmless row until a question takes it: one own token at position 0 of its (zeroed) slot
@@ -1679,68 +1607,45 @@ class VddLlavaEngine:
                 for i, f in zip(todo, self.image_features([images[i] for i in todo])):
                     feat_of[id(images[i])] = f
             new_pre, suffix, dec = [], [], []
-            for b, nm in enumerate(names if emb_mode else []):
+            for b, nm in enumerate(names):
                 for q, i in zip(slots, qs):
-                    e_, (key, P) = emb_all[i], emb_pre[i]
-                    T_, row, pslot = int(e_.shape[0]), b * Qc + q, 0
+                    if emb_mode:
+                        e_, (key, P) = emb_all[i], emb_pre[i]
+                        pre, own = dict(tokens=[], img=e_[:P]), dict(tokens=None, pre=[], img=e_[P:], suf=[], T=int(e_.shape[0]) - P)
+                    else:
+                        r, si = ids_all[i], s_img[i]
+                        toks, suf = slot_cut(nm, r, si)
+                        if nm == "main":
+                            key, P, pre = ("img", tuple(r[:si]), id(images[i])), si + n_img_tok, dict(tokens=toks, img=feat_of[id(images[i])])
+                        else:
+                            key, P, pre = (nm, tuple(r[:si])), len(toks), dict(tokens=toks, img=None)
+                        own = dict(tokens=suf, img=None, T=len(suf))
+                    pslot, row = 0, b * Qc + q
                     if key is not None:
                         e = table.get(key)
                         if e is None:
                             e = table[key] = dict(slot=free_pre.pop(), ref=0, T=P)
-                            new_pre.append(dict(slot=e["slot"], tokens=[], img=e_[:P], T=P, pos0=0, pslot=0, plen=0))
+                            new_pre.append(dict(pre, slot=e["slot"], T=P, pos0=0, pslot=0, plen=0))
                         e["ref"] += 1
                         slot_keys[q].append(key)
                         pslot = e["slot"]
-                    suffix.append(dict(slot=row, tokens=None, pre=[], img=e_[P:], suf=[], T=T_ - P, pos0=P, pslot=pslot, plen=P))
-                    dec.append((T_, T_ - P, [row, T_ + 1, pslot, P]))
-            for b, nm in enumerate([] if emb_mode else names):
-                for q, i in zip(slots, qs):
-                    r, si = ids_all[i], s_img[i]
-                    if nm == "main":
-                        key, toks, img, T = ("img", tuple(r[:si]), id(images[i])), r[:si], feat_of[id(images[i])], si + n_img_tok
-                    elif nm == "unk":
-                        key, toks, img, T = ("unk", tuple(r[:si])), r[:si] + [0], None, si + 1       # the <unk> token stays in the prefix (quirk #3)
-                    else:
-                        key, toks, img, T = ("none", tuple(r[:si])), r[:si], None, si
-                    e = table.get(key)
-                    if e is None:
-                        e = table[key] = dict(slot=free_pre.pop(), ref=0, T=T)
-                        new_pre.append(dict(slot=e["slot"], tokens=toks, img=img, T=T, pos0=0, pslot=0, plen=0))
-                    e["ref"] += 1
-                    slot_keys[q].append(key)
-                    suf = r[si + 1:]
-                    row = b * Qc + q
-                    suffix.append(dict(slot=row, tokens=suf, img=None, T=len(suf), pos0=T, pslot=e["slot"], plen=T))
-                    dec.append((T + len(suf), len(suf), [row, T + len(suf) + 1, e["slot"], T]))
+                    suffix.append(dict(own, slot=row, pos0=P, pslot=pslot, plen=P))
+                    dec.append((P + own["T"], own["T"], [row, P + own["T"] + 1, pslot, P]))
             for q, i in zip(slots, qs):
                 slot_q[q] = i
-            passes = []
-            if new_pre:
-                x, pos, cpos, slot, seqs, max_tq = self._pack(new_pre)
-                passes.append(dict(x=x, pos=pos, cpos=cpos, slot=slot, seqs=seqs, n_seq=len(new_pre), max_tq=max_tq, to_prefix_pool=True, keep_q=False))
+            passes = [self._prefill_pass(new_pre, to_prefix_pool=True)] if new_pre else []
             scratch = []
             if vcd:
-                # fresh noise per question (llava_sampling.py:88-91): no feature cache, but whole tower chunks
-                f_cd = []
-                for i0 in range(0, len(qs) if not emb_mode else 0, self.VIT_CHUNK):
-                    f_cd += list(self.vit(torch.stack([images_cd[i].reshape(images_cd[i].shape[-3:]).to(dev) for i in qs[i0:i0 + self.VIT_CHUNK]])))
                 scratch = [free_pre.pop() for _ in qs]
                 if emb_mode:          # images_cd = the noisy-image EMBEDDINGS of the whole prompt (modeling_llama.py:778-782, modeling_qwen.py:1089-1118)
                     cd_seq = [dict(slot=sl, tokens=[], img=emb_cd_all[i], T=int(emb_cd_all[i].shape[0]), pos0=0, pslot=0, plen=0) for sl, i in zip(scratch, qs)]
-                else:
-                    cd_seq = [dict(slot=sl, tokens=ids_all[i][:s_img[i]], img=f, suf=ids_all[i][s_img[i] + 1:], T=len(ids_all[i]) - 1 + n_img_tok, pos0=0,
-                                   pslot=0, plen=0) for sl, i, f in zip(scratch, qs, f_cd)]
-                x, pos, cpos, slot, seqs, max_tq = self._pack(cd_seq)
-                last, last_seqs = h2d_int32(dev, [s_["q_row0"] + s_["T"] - 1 for s_ in cd_seq], [[j, 1, s_["T"] - 1, s_["slot"], 0, 0] for j, s_ in enumerate(cd_seq)])
-                passes.append(dict(x=x, pos=pos, cpos=cpos, slot=slot, seqs=seqs, n_seq=len(cd_seq), max_tq=max_tq, to_prefix_pool=True, last_rows=last.long(),
-                                   last_seqs=last_seqs, keep_q=False))
-            x, pos, cpos, slot, seqs, max_tq = self._pack(suffix)
-            packs_h = ops.flash_packs([[0, 0, 0, 0, s_["pslot"], s_["plen"]] for s_ in suffix]) if (max_tq <= 32 and (not ops.GEMM_BATCH_INVARIANT or ops.FLASH_PACKS_IN_INVARIANT_MODE)) else None
-            last, last_seqs, packs = h2d_int32(dev, [s_["q_row0"] + s_["T"] - 1 for s_ in suffix],
-                                               [[j, 1, s_["pos0"] + s_["T"] - 1, s_["slot"], s_["pslot"], s_["plen"]] for j, s_ in enumerate(suffix)],
-                                               packs_h if packs_h is not None else [[0, -1, -1, -1]])
-            passes.append(dict(x=x, pos=pos, cpos=cpos, slot=slot, seqs=seqs, n_seq=len(suffix), max_tq=max_tq, to_prefix_pool=False, last_rows=last.long(),
-                               last_seqs=last_seqs, packs=packs if packs_h is not None else None, keep_q=False))
+                else:                 # fresh noise per question (llava_sampling.py:88-91)
+                    cd_seq = []
+                    for sl, i, f in zip(scratch, qs, self._noised_features([images_cd[i] for i in qs])):
+                        pre, suf = slot_cut("cd", ids_all[i], s_img[i])
+                        cd_seq.append(dict(slot=sl, tokens=pre, img=f, suf=suf, T=len(pre) + n_img_tok + len(suf), pos0=0, pslot=0, plen=0))
+                passes.append(self._prefill_pass(cd_seq, to_prefix_pool=True, last=True))
+            passes.append(self._prefill_pass(suffix, to_prefix_pool=False, last=True, packs=True))
             outs = self.lm.prefill(passes, kv)
             resid, delta = outs[-1]
             logits0 = self.lm.logits(resid, delta)                                  # [nb * k, V], branch-major
@@ -1785,16 +1690,10 @@ class VddLlavaEngine:
         while True:
             run.step(kv)
             steps += 1
-            if steps % self.LAUNCH_WINDOW == 0:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                marks.append(ev)
-                if len(marks) > 1:
-                    marks.pop(0).synchronize()
+            self._throttle(steps, marks)
             if steps % sync_every and not (steps in (1, 3) and sync_every > 2):
                 continue
-            state = torch.cat([run.unfinished, (run.status | run.status0).ne(0).any().long()[None]]).tolist()    # ONE sync
-            unf_h, bad = state[:-1], state[-1]
+            unf_h, bad = run.poll()
             live_row_steps += nb * sum(unf_h) * min(sync_every, steps)
             if bad:
                 break
@@ -1818,15 +1717,13 @@ class VddLlavaEngine:
             if len(free) >= min(admit_min, len(waiting)) or not any(unf_h):
                 retire(done)
                 timed_admit(free[:len(waiting)])
-        if bool((run.status | run.status0).ne(0).any().item()):
-            raise RuntimeError("probability tensor contains either `inf`, `nan` or element < 0")   # torch.multinomial, vcd_sample.py:202
+        run.raise_if_failed()
         retire([q for q in range(run.Q) if slot_q[q] >= 0])
         stats.update(admit_gpu_s=round(sum(a_.elapsed_time(b_) for a_, b_ in ev_pairs) / 1e3, 3), admit_host_s=round(host_admit, 3))
-        is_eos = (master[:, :, None] == eos_t[None, None, :]).any(-1)
-        n_tok = torch.where(is_eos.any(1), is_eos.float().argmax(1) + 1, torch.full((N,), max_new_tokens, device=dev))
-        gen = master[:, : int(n_tok.max().item())].clone()
+        gen, done_at = self._trim_after_all_finished(master, eos_t)
+        gen = gen.clone()
         seqs_out = prompt_plus_answer(dev, ids_all, gen)        # (embedding prompts: ids_all is empty per question - the new tokens alone)
-        stats.update(steps=steps, graph=run.graph is not None, answer_tokens=int(n_tok.sum().item()),
+        stats.update(steps=steps, graph=run.graph is not None, answer_tokens=int(done_at.sum().item()) + N,
                      mean_live_rows=round(live_row_steps / max(steps, 1), 1), n_groups=0)
         return GenerateOutput(seqs_out, gen, None, top_prob, top_tok, stats)
 
@@ -1916,6 +1813,105 @@ class VddLlavaEngine:
             self._graphs[key] = r
         return r
 
+    # -- pieces of generate() and generate_list() ----------------------------------------------------------------------------------
+    def _drop_graphs(self, kv):                 # the decode steps captured over the pools `kv` point into them
+        self._graphs = {k: r for k, r in self._graphs.items() if r.kv is not kv}
+
+    def _drop_retired_runner(self, cfgkey):     # generate()'s last retirement / growth event: nothing replays its runner again
+        self._graphs = {k: r for k, r in self._graphs.items() if not (len(k) > len(cfgkey) and k[len(cfgkey)] == "retired")}
+
+    def _forget_kept_prefill(self, kv):         # a prefill into the pools `kv` overwrites the state a reuse_prefill call kept there
+        if self._prefill_cache is not None and self._prefill_cache["kv"] is kv:
+            self._prefill_cache = None
+
+    # reuse_prefill: a sweep over sampling settings (the reference's scripts run 51 of them over the same questions, MME/run_llava.py:281-318)
+    # asks for the SAME prompts again - only the warpers / seed / alpha / beta differ, and none of them enters the prefill.  The call keeps
+    # its plan, pools and step-0 logits; the next reuse_prefill call with the same prompt and image tensors (the caller's promise: unchanged),
+    # the same branches and no more new tokens skips the vision tower and the prefill and decodes again from that state (a decode only writes
+    # own-KV positions behind the prompt).  Not with the VCD branch (fresh noise per call); such calls never retire rows.
+    def _reuse_lookup(self, ids_list, images, embs, embeds_prefix, branch_flags, share_prefix, max_new_tokens):
+        """-> (the kept state if it serves this call, else None; the key to keep this call's state under)"""
+        ims = None if images is None else tuple((images[i].data_ptr(), tuple(images[i].shape)) for i in range(len(ids_list)))
+        embs = None if embs is None else tuple((e.data_ptr(), tuple(e.shape)) for e in embs)
+        key = (tuple(map(tuple, ids_list)), ims, embs, tuple(embeds_prefix) if embeds_prefix is not None else None, branch_flags, share_prefix,
+               self.two_level_prefix, self.share_repeated_rows, self.group_attention, ops.GEMM_BATCH_INVARIANT, str(self.dtype))
+        c = self._prefill_cache
+        hit = c is not None and c["key"] == key and self._kvs.get(c["frag"]) is c["kv"] and max_new_tokens <= c["max_new"]
+        return (c if hit else None), key
+
+    def _reuse_store(self, key, kv, frag, plan, branches, logits0, max_new_tokens):
+        self._prefill_cache = dict(key=key, kv=kv, frag=frag, plan=plan, branches=branches, logits0=logits0, max_new=max_new_tokens)
+
+    def _noised_features(self, images_cd):
+        """The VCD branch's noised images differ per question (fresh noise, llava_calibrate.py:152-155): no feature cache, but whole
+        tower chunks instead of one launch chain per question."""
+        feats = []
+        for i0 in range(0, len(images_cd), self.VIT_CHUNK):
+            feats += list(self.vit(torch.stack([im.reshape(im.shape[-3:]).to(self.device) for im in images_cd[i0:i0 + self.VIT_CHUNK]])))
+        return feats
+
+    def _prefill_pass(self, segs, to_prefix_pool, last=False, packs=False, keep_q=False):
+        """The LanguageModel.prefill pass over `segs` (_pack writes their q_row0).  last: one-query descriptors of every sequence's last row
+        (prefill returns their state); packs: short suffixes behind shared prefixes, four of one prefix per workgroup (ops.flash_packs)."""
+        x, pos, cpos, slot, seqs, max_tq = self._pack(segs)
+        pd = dict(x=x, pos=pos, cpos=cpos, slot=slot, seqs=seqs, n_seq=len(segs), max_tq=max_tq, to_prefix_pool=to_prefix_pool, keep_q=keep_q)
+        if last:
+            packs_h = (ops.flash_packs([[0, 0, 0, 0, s["pslot"], s["plen"]] for s in segs]) if packs and max_tq <= 32 and self.cfg.lm.head_dim == 128
+                       and (not ops.GEMM_BATCH_INVARIANT or ops.FLASH_PACKS_IN_INVARIANT_MODE) else None)
+            last_rows, last_seqs, packs_d = h2d_int32(self.device, [s["q_row0"] + s["T"] - 1 for s in segs],
+                                                      [[i, 1, s["pos0"] + s["T"] - 1, s["slot"], s["pslot"], s["plen"]] for i, s in enumerate(segs)],
+                                                      packs_h if packs_h is not None else [])
+            pd.update(last_rows=last_rows.long(), last_seqs=last_seqs, packs=packs_d if packs_h is not None else None)
+        return pd
+
+    def _attention_map(self, plan, passes, kv):
+        """output_attentions, one question: the last layer's map [1, H, T, T] (like HF's attention weights) of the main branch's prompt
+        (suffix sequence 0 + its prefix slot) from the rotated queries the prefill kept (keep_q, dropped here) and the cached keys."""
+        lm, s0 = self.cfg.lm, plan["suffix"][0]
+        q_rows = [passes[-1]["q_last"][s0["q_row0"]: s0["q_row0"] + s0["T"]]]
+        if s0["plen"] > 0:
+            p0 = plan["prefix"][s0["pslot"]]
+            q_rows.insert(0, passes[0]["q_last"][p0["q_row0"]: p0["q_row0"] + p0["T"]])
+        q_full = torch.cat(q_rows, 0) if len(q_rows) > 1 else q_rows[0].contiguous()
+        m = ops.attention_probs(q_full, kv.ko[-1], (0, q_full.shape[0], 0, s0["slot"], s0["pslot"], s0["plen"]), lm.n_heads, lm.n_kv_heads,
+                                lm.head_dim, k_prefix=kv.kp[-1])
+        for p_ in passes:
+            p_.pop("q_last", None)
+        return m[None]
+
+    @staticmethod
+    def _philox_counter(seed) -> int:
+        """Device-side Philox counter = (stream, step): graphs are seed-agnostic.  seed=None: the stream id is drawn from torch's default
+        generator, so every call samples fresh numbers (the reference's torch.multinomial advances the generator too) and torch.manual_seed()
+        reproduces a run's random numbers; an explicit seed is a pure function of the seed.  (The bf16 logits they are applied to depend, in
+        their last bits, on the GEMM schedule the tuner picked: ops.gemm_choices_export.)"""
+        from .sampling import fresh_offset
+        return ((fresh_offset() if seed is None else int(seed)) & 0x3FFFFFFFFF) << 24
+
+    def _throttle(self, n_steps, marks):
+        """After every decode step.  The host runs ahead of the device (a captured step is one graph launch): a 256-token generation used to
+        leave > 100,000 kernel packets queued, and rocprofv3 aborted the process once ~30 - 60 thousand were outstanding
+        (tools/rocprof_abort_bisect.py).  So the loop waits for the step launched LAUNCH_WINDOW steps ago: at most 2 x 16 steps in flight."""
+        if n_steps % self.LAUNCH_WINDOW == 0:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+            marks.append(ev)
+            if len(marks) > 1:
+                marks.pop(0).synchronize()
+
+    def _retire_rows(self, run, live_q, n_new, own_len, t_own, cfgkey, event):
+        """One retirement / growth event of generate(): a new runner, kept under cfgkey + ('retired', ...), continues `run` with its questions
+        live_q only; their rows move to the front of the own pools, repacked to t_own tokens per slot (own_len: the live rows of a slot)."""
+        kv, lm, Qn = run.kv, self.cfg.lm, len(live_q)
+        q_idx = torch.tensor(live_q, dtype=torch.long, device=self.device)
+        self._drop_graphs(kv)
+        new_run = _DecodeRunner(self, Qn, run.nb, run.max_new, dict(run.tail), kv)
+        kv.repack_own(new_run.adopt(run, q_idx, n_new), own_len, t_own)
+        new_run.workspace = ops.attention_workspace(run.nb * Qn, lm.n_heads, lm.head_dim, kv.t_pre + (kv.t_own + 63) // 64 * 64, self.device)
+        self._drop_retired_runner(cfgkey)
+        self._graphs[cfgkey + ("retired", Qn, kv.t_own, event)] = new_run
+        return new_run
+
     two_level_prefix = True      # [system prompt] prefilled once, the image prefixes behind it (False: every [sys + image] prefix in full)
 
     @staticmethod
@@ -1944,12 +1940,13 @@ class VddLlavaEngine:
         plan["prefill_tokens"] -= n * (len(members) - 1)
 
     @staticmethod
-    def _trim_after_all_finished(gen, eos_t, pad):
+    def _trim_after_all_finished(gen, eos_t):
         """The reference stops at the first step after which every row has emitted EOS (:291); we check every
-        `sync_every` steps, so cut the surplus all-pad columns to return exactly what it returns."""
+        `sync_every` steps, so cut the surplus all-pad columns to return exactly what it returns.  Returns the cut tokens (a view) and
+        the column of every row's last answer token (its first EOS, else the last column)."""
         is_eos = (gen[:, :, None] == eos_t[None, None, :]).any(-1)
         done_at = torch.where(is_eos.any(1), is_eos.float().argmax(1), torch.full((gen.shape[0],), gen.shape[1] - 1, device=gen.device))
-        return gen[:, : int(done_at.max().item()) + 1]
+        return gen[:, : int(done_at.max().item()) + 1], done_at
 
     # -- prefill planning ---------------------------------------------------------------------------------
     def _plan(self, branches, n_img_tok, share_prefix, embeds_only=False, embeds_prefix=None):
@@ -2013,17 +2010,17 @@ class VddLlavaEngine:
                 s_img = src.index(IMAGE_TOKEN_INDEX) if IMAGE_TOKEN_INDEX in src else None
                 img = feats[qi] if (feats is not None and s_img is not None) else None
                 if img is not None:                          # main / cd: [tokens before the slot | 576 patch embeddings]
-                    pre_tok, suf_tok, plen = ids[:s_img], ids[s_img + 1:], s_img + n_img_tok
-                    key = (tuple(pre_tok), img.data_ptr())
+                    pre_tok, suf_tok = slot_cut(name, src, s_img)
+                    plen, key = s_img + n_img_tok, (tuple(pre_tok), img.data_ptr())
                 else:
                     if repeated and tuple(ids) in repeated:
-                        cut = len(ids) - 1
+                        pre_tok, suf_tok = ids[:-1], ids[-1:]
                     elif s_img is None:
                         cut = self._common_split(rows) if share_prefix else 0
+                        pre_tok, suf_tok = ids[:cut], ids[cut:]
                     else:
-                        cut = s_img + 1 if name == "unk" else s_img     # unk keeps the one <unk> token in the prefix (quirk #3)
-                    pre_tok, suf_tok, plen = ids[:cut], ids[cut:], cut
-                    key = (tuple(pre_tok), None)
+                        pre_tok, suf_tok = slot_cut(name, src, s_img)
+                    plen, key = len(pre_tok), (tuple(pre_tok), None)
                 total = plen + len(suf_tok)
                 unshared += total
                 max_len = max(max_len, total)
