@@ -19,16 +19,17 @@ Tokenisers stay with the caller: `tokenize_llm(prompt) -> ids` (the Vicuna token
 from __future__ import annotations
 
 import json
-from typing import Callable, Dict, List, Optional, Sequence
+from typing import Callable, List, Optional, Sequence
 
 import torch
 
 from . import calibrate as C
+from . import shard
 from .blip_frontend import InstructBlipFrontEnd
+from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, add_script_args, answer_text, chunk_of, distinct, eos_set, finish_distributed, load_distinct_images,
+                            pope_scores_for, read_questions, to_all_rows, write_jsonl)
 from .engine import VddLlavaEngine
 from .vcd_add_noise import add_diffusion_noise
-
-QUESTION_SUFFIX = " Please answer this question with one word."      # blip_calibrate.py:42,74
 
 
 def map_pad_to_eos(tokens: torch.Tensor) -> torch.Tensor:
@@ -54,39 +55,23 @@ def run_blip_pope(engine: VddLlavaEngine, front: InstructBlipFrontEnd, questions
     its chunk of whole images (shard.ShardPlan; BASELINE config #5 runs on 4 GPUs), ONE collective gathers the results, rank 0 writes
     the file, every rank returns the full result.  Returns {"answers": [...], "scores": {...}}; the JSONL has the reference's
     fields (question_id, prompt, text, model_id, image, naive, noise, zeros, metadata; blip_calibrate.py:100-109)."""
-    import contextlib
-    from . import ops
-    from .pope_driver import ResultRows, cut_at_eos
-    from .shard import ShardPlan, resolve_batch_invariant
-    order = sorted(range(len(questions)), key=lambda i: (questions[i]["image"], i))
-    plan = ShardPlan([questions[i]["image"] for i in order], rank, world)
-    mine = [order[p_] for p_ in plan.mine]
-    if generate_kw.get("seed") is not None:
-        generate_kw = dict(generate_kw, seed=int(generate_kw["seed"]) + plan.rank)
+    run = ShardedRun(questions, rank, world, generate_kw, batch_invariant)      # (invariant mode: the LM side; the EVA-ViT / Q-Former front-end is per image / per question)
     decode_token = lambda t: decode([t])
     embed = engine.w.t["embed"]
-    eos_set = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
     base_kw = dict(do_sample=True, top_p=top_p, top_k=top_k, temperature=temperature, num_beams=1, repetition_penalty=repetition_penalty,
                    min_length=min_length, eos_token_id=eos_token_id, pad_token_id=pad_token_id, n_top=10, cd_beta=cd_beta,
-                   cd_alpha=cd_alpha, **generate_kw)
-    rows = ResultRows(engine.device, max_length, pad_token_id if pad_token_id is not None else 0, n_sets=3)
-    invariant = resolve_batch_invariant(batch_invariant, plan.world, generate_kw)    # (the LM side; the EVA-ViT / Q-Former front-end is per image / per question)
-    with (ops.batch_invariant() if invariant else contextlib.nullcontext()):
-        for b0 in range(0, len(mine), batch_questions):
-            idx = mine[b0:b0 + batch_questions]
-            qs = [questions[i] for i in idx]
+                   cd_alpha=cd_alpha, **run.generate_kw)
+    rows = run.rows(engine.device, max_length, pad_token_id, n_sets=3)
+    with run.mode():
+        for idx, qs in run.batches(batch_questions):
             prompts = [q["text"] + QUESTION_SUFFIX for q in qs]
             llm_ids = [tokenize_llm(p) for p in prompts]
             qf_ids = [tokenize_qformer(p) for p in prompts]
-            cache: Dict[str, torch.Tensor] = {}
-            for q in qs:
-                if q["image"] not in cache:
-                    cache[q["image"]] = load_image(q["image"]).to(engine.device)
+            loaded = load_distinct_images([q["image"] for q in qs], load_image, engine.device)
             # EVA-ViT once per DISTINCT clean image and once for the `zeros` image; the noised copies are drawn per question (fresh noise inside
             # the reference's loop, blip_calibrate.py:80-82, :96) and so are their ViT passes; the Q-Former reads the instruction: per question
-            names = list(cache)
-            where = [names.index(q["image"]) for q in qs]
-            uniq = torch.stack([cache[n] for n in names])
+            pick, where = distinct([q["image"] for q in qs])
+            uniq = torch.stack([loaded[i] for i in pick])
             ie_u = front.image_embeds(uniq)
             ie_main = ie_u[where]
             imgs = uniq[where]
@@ -99,37 +84,22 @@ def run_blip_pope(engine: VddLlavaEngine, front: InstructBlipFrontEnd, questions
             noise999 = torch.stack([add_diffusion_noise(im, 999) for im in imgs])
             emb_n = front.assemble(front.embeds_to_llm(front.image_embeds(noise999), qf_ids), llm_ids, embed)
             # the zero image's prior depends on the question text alone (POPE repeats its texts over the images): Q-Former + LLM once per distinct prompt
-            first_z: Dict[str, int] = {}
-            where_z = [first_z.setdefault(p, len(first_z)) for p in prompts]
-            pick_z = [prompts.index(p) for p in first_z]
+            pick_z, where_z = distinct(prompts)
             ie_zero = front.image_embeds(torch.zeros_like(uniq[:1])).expand(len(pick_z), -1, -1).contiguous()
             emb_z = front.assemble(front.embeds_to_llm(ie_zero, [qf_ids[j] for j in pick_z]), [llm_ids[j] for j in pick_z], embed)
             prior_kw = {k: v for k, v in base_kw.items() if k not in ("cd_beta", "cd_alpha")}
             noise = engine.generate(None, inputs_embeds=emb_n, max_length=1, **prior_kw)
             zeros = engine.generate(None, inputs_embeds=emb_z, max_length=1, **prior_kw)
-            back_z = torch.tensor(where_z, dtype=torch.long).to(zeros.top_tok.device, non_blocking=True)
-            rows.add(idx, map_pad_to_eos(main.tokens), [(main.top_tok, main.top_prob), (noise.top_tok, noise.top_prob), (zeros.top_tok[back_z], zeros.top_prob[back_z])])
-    got = rows.gather(plan, len(questions))                    # ONE collective; every rank holds every question's results behind it
+            rows.add(idx, map_pad_to_eos(main.tokens), [(main.top_tok, main.top_prob), (noise.top_tok, noise.top_prob), to_all_rows(zeros, where_z)])
+    got = run.gather(rows)
+    eos = eos_set(eos_token_id)
     dicts = [[C.label_dict_from_top(t, p_, decode_token) for t, p_ in got["tops"][s_]] for s_ in range(3)]
-    ordered = [{"question_id": q["question_id"], "prompt": q["text"] + QUESTION_SUFFIX, "text": decode(cut_at_eos(got["tokens"][i], eos_set)).strip(),
+    ordered = [{"question_id": q["question_id"], "prompt": q["text"] + QUESTION_SUFFIX, "text": answer_text(decode, got["tokens"][i], eos),
                 "model_id": model_id, "image": q["image"], "naive": dicts[0][i], "noise": dicts[1][i], "zeros": dicts[2][i], "metadata": {}}
                for i, q in enumerate(questions)]
-    if plan.rank != 0:
-        answers_path = None                                    # rank 0 owns the file
-    if answers_path is not None:
-        with open(answers_path, "w") as f:
-            for a in ordered:
-                f.write(json.dumps(a) + "\n")
-    scores = {}
-    if all("label" in q for q in questions):
-        gt = [{"question_id": q["question_id"], "label": q["label"]} for q in questions]
-        for name, fn, args in (("string_match", C.pope_scores, ()), ("naive", C.pope_scores_calibrated, ("naive",)),
-                               ("noise", C.pope_scores_calibrated, ("noise",)), ("zeros", C.pope_scores_calibrated, ("zeros",))):
-            try:
-                scores[name] = fn(gt, ordered, *args)
-            except ZeroDivisionError:
-                scores[name] = None
-    return {"answers": ordered, "scores": scores, "batch_invariant": invariant}
+    if answers_path is not None and run.rank == 0:             # rank 0 owns the file
+        write_jsonl(answers_path, ordered)
+    return {"answers": ordered, "scores": pope_scores_for(questions, ordered, ("string_match", "naive", "noise", "zeros")), "batch_invariant": run.invariant}
 
 
 LAVIS_MEAN, LAVIS_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
@@ -145,6 +115,19 @@ def blip_image_eval(path: str, size: int = 224) -> torch.Tensor:
     return (x - torch.tensor(LAVIS_MEAN)[:, None, None]) / torch.tensor(LAVIS_STD)[:, None, None]
 
 
+def _parser():
+    import argparse
+    ap = argparse.ArgumentParser()
+    add_common_args(ap, image_folder="", temperature=1.0, top_p=1.0, seed=42)
+    add_script_args(ap)
+    ap.add_argument("--blip-checkpoint", required=True)
+    ap.add_argument("--llm-path", required=True)
+    ap.add_argument("--bert-tokenizer", required=True)
+    ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--max_txt_len", type=int, default=128)
+    return ap
+
+
 def main(argv=None):
     """python -m llava_align_amd.blip_driver --blip-checkpoint instruct_blip_vicuna7b.pth --llm-path vicuna-7b-v1.1 --bert-tokenizer bert-base-uncased
     --image-folder IMGS --question-file coco_pope_adversarial.json --answers-file OUT.jsonl [--use_cd --noise_step 500 --cd_beta 0.1 --top_p 1
@@ -154,37 +137,13 @@ def main(argv=None):
     safetensors), the Vicuna directory (HF weights + tokenizer) and the BERT tokenizer the Q-Former reads the instruction with.
     --cd_alpha is accepted and NOT forwarded, as in the reference (the sampler's 0.5 applies); --temperature / --top_k / --conv-mode
     are parsed and unused there too.  Under torchrun: one rank per GPU (BASELINE config #5 runs on 4), whole images per rank, one gather."""
-    import argparse
     import os
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--blip-checkpoint", required=True)
-    ap.add_argument("--llm-path", required=True)
-    ap.add_argument("--bert-tokenizer", required=True)
-    ap.add_argument("--model-base", default=None)
-    ap.add_argument("--image-folder", default="")
-    ap.add_argument("--question-file", required=True)
-    ap.add_argument("--answers-file", required=True)
-    ap.add_argument("--conv-mode", default="llava_v1")
-    ap.add_argument("--num-chunks", type=int, default=1)
-    ap.add_argument("--chunk-idx", type=int, default=0)
-    ap.add_argument("--temperature", type=float, default=1.0)
-    ap.add_argument("--top_p", type=float, default=1.0)
-    ap.add_argument("--top_k", type=int, default=None)
-    ap.add_argument("--noise_step", type=int, default=500)
-    ap.add_argument("--use_cd", action="store_true")
-    ap.add_argument("--cd_alpha", type=float, default=1.0)
-    ap.add_argument("--cd_beta", type=float, default=0.1)
-    ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--batch", type=int, default=128)
-    ap.add_argument("--max_txt_len", type=int, default=128)
-    ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16")
-    a = ap.parse_args(argv)
+    a = _parser().parse_args(argv)
     from . import checkpoint as K
     from .blip_frontend import BlipWeights
     from .engine import LlavaWeights
     from .hf_adapter import blip_config_from_model
-    from .shard import get_chunk, init_from_env
-    rank, world, device = init_from_env()
+    rank, world, device = shard.init_from_env()
     dtype = getattr(torch, a.dtype)
     sd = K.load_state_dict(a.blip_checkpoint)
     bcfg = blip_config_from_model(None, sd)
@@ -195,10 +154,7 @@ def main(argv=None):
     llm_tok = K.load_tokenizer(a.llm_path)
     from transformers import AutoTokenizer
     bert = AutoTokenizer.from_pretrained(a.bert_tokenizer)
-    questions = [json.loads(q) for q in open(os.path.expanduser(a.question_file))]
-    if a.num_chunks > 1:
-        questions = [questions[i] for i in get_chunk(len(questions), a.num_chunks, a.chunk_idx, group=1)]
-    os.makedirs(os.path.dirname(os.path.abspath(os.path.expanduser(a.answers_file))), exist_ok=True)
+    questions = chunk_of(read_questions(a.question_file), a)
     size = bcfg.vit.image
     res = run_blip_pope(eng, front, questions, lambda p: llm_tok(p).input_ids,
                         lambda p: bert(p, truncation=True, max_length=a.max_txt_len).input_ids,
@@ -208,10 +164,7 @@ def main(argv=None):
     if rank == 0:
         nan = {k: v["nan_rows"] for k, v in res["scores"].items() if isinstance(v, dict) and v.get("nan_rows")}
         print(json.dumps({"scores": res["scores"], "n_answers": len(res["answers"]), "rows_whose_calibrated_vector_is_nan": nan}, indent=1))
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
+    finish_distributed(world)
 
 
 if __name__ == "__main__":

@@ -23,7 +23,11 @@ from typing import Callable, Dict, List, Optional, Sequence
 import torch
 
 from . import calibrate as C
+from . import shard
+from .driver_common import (ShardedRun, add_common_args, add_script_args, answer_text, eos_set, finish_distributed, plain_kw, read_questions, setting_kw,
+                            sweep_result, sweep_settings, write_jsonl)
 from .engine import IMAGE_TOKEN_INDEX, VddLlavaEngine
+from .vcd_add_noise import add_diffusion_noise
 
 MME_SUBSETS = ("existence", "count", "position", "color", "commonsense_reasoning", "numerical_calculation", "text_translation",
                "code_reasoning")                                                   # run_qwen.py:146, run_llava.py:133
@@ -117,33 +121,19 @@ def run_mme(engine: VddLlavaEngine, questions: Sequence[dict], build_inputs: Cal
     prefill), each decodes from that state with its own warpers.  Returns {"runs": {tag: the per-setting result}}; not with the VCD branch
     (its noise is drawn per call), which decodes every setting from scratch.
     Returns {"answers": [...], "results": {name: dir}, "scores": {name: mme_scores}}."""
-    import contextlib
-    from . import ops
-    from .shard import get_chunk, resolve_batch_invariant
     qs_all = [q for q in questions if subsets is None or q.get("category") in subsets]
     if chunk is not None:
-        qs_all = [qs_all[i] for i in get_chunk(len(qs_all), chunk[0], chunk[1], group=1)]
-    from .pope_driver import ResultRows, cut_at_eos
-    from .shard import ShardPlan
-    order = sorted(range(len(qs_all)), key=lambda i: (qs_all[i]["image"], i))          # an image's two questions adjacent: shared features
-    plan = ShardPlan([qs_all[i]["image"] for i in order], rank, world)
-    mine = [order[p_] for p_ in plan.mine]
+        qs_all = [qs_all[i] for i in shard.get_chunk(len(qs_all), chunk[0], chunk[1], group=1)]
+    run = ShardedRun(qs_all, rank, world, generate_kw, batch_invariant)       # an image's two questions adjacent: shared features
     decode_token = lambda t: decode([t])
-    eos_set = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
-    if generate_kw.get("seed") is not None:
-        generate_kw = dict(generate_kw, seed=int(generate_kw["seed"]) + plan.rank)
-    settings = [dict(tag=None)] if sweep is None else [dict(s_) for s_ in sweep]
+    settings = sweep_settings(sweep)
     if not settings:
         raise ValueError("sweep: at least one setting")
-    over = lambda s_: {k: s_[k] for k in ("temperature", "top_p", "top_k") if k in s_}
-    kws = [dict(generate_kw, **over(s_)) for s_ in settings]
+    kws = [setting_kw(run.generate_kw, s_) for s_ in settings]
     keep = len(settings) > 1 and noise_step is None            # the settings of a batch decode from ONE prefill
-    all_rows = [ResultRows(engine.device, max_new_tokens, pad_token_id if pad_token_id is not None else 0, n_sets=3) for _ in settings]
-    invariant = resolve_batch_invariant(batch_invariant, plan.world, generate_kw)
-    with (ops.batch_invariant() if invariant else contextlib.nullcontext()):
-        for b0 in range(0, len(mine), batch_questions):
-            idx = mine[b0:b0 + batch_questions]
-            lines = [qs_all[i] for i in idx]
+    all_rows = [run.rows(engine.device, max_new_tokens, pad_token_id, n_sets=3) for _ in settings]
+    with run.mode():
+        for idx, lines in run.batches(batch_questions):
             img_cache: Dict[str, dict] = {}
             if getattr(build_inputs, "prepare", None) is not None:
                 build_inputs.prepare(lines)
@@ -161,7 +151,6 @@ def run_mme(engine: VddLlavaEngine, questions: Sequence[dict], build_inputs: Cal
             for j, kw_s in enumerate(kws):
                 kw = dict(kw_s)
                 if noise_step is not None and "image" in mains[0]:
-                    from .vcd_add_noise import add_diffusion_noise
                     kw["images_cd"] = [add_diffusion_noise(img_cache[l["image"]]["image"].to(engine.device), noise_step) for l in lines]   # run_llava.py:187-190
                 outs[j][0] = _generate(engine, mains, max_new_tokens=max_new_tokens, n_top=10, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                        min_new_tokens=min_new_tokens, reuse_prefill=keep, **kw)
@@ -169,35 +158,27 @@ def run_mme(engine: VddLlavaEngine, questions: Sequence[dict], build_inputs: Cal
             # the reference's calibration calls (run_qwen.py:111-131)
             for which, inputs in ((1, nones), (2, unks)):
                 for j, kw_s in enumerate(kws):
-                    prior_kw = dict(max_new_tokens=1, n_top=10, **{k: v for k, v in kw_s.items() if k in ("temperature", "top_p", "top_k", "seed", "cd_alpha", "cd_beta")})
+                    prior_kw = dict(max_new_tokens=1, n_top=10, **plain_kw(kw_s))
                     if min_new_tokens:
                         prior_kw.update(min_new_tokens=min_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id)
                     outs[j][which] = _generate(engine, inputs, reuse_prefill=keep, **prior_kw)
             for j in range(len(settings)):
                 all_rows[j].add(idx, outs[j][0].tokens, [(o.top_tok, o.top_prob) for o in outs[j]])
             engine.clear_image_cache()
+    eos = eos_set(eos_token_id)
 
     def finish(rows, answers_path, experiment):
-        got = rows.gather(plan, len(qs_all))                   # ONE collective per setting; every rank holds every question's results behind it
+        got = run.gather(rows)                                 # (one collective per setting)
         dicts = [[C.label_dict_from_top(t, p_, decode_token) for t, p_ in got["tops"][s_]] for s_ in range(3)]
-        answers = []
-        for i, line in enumerate(qs_all):
-            text = decode(cut_at_eos(got["tokens"][i], eos_set)).strip()
-            if stop_str and text.endswith(stop_str):
-                text = text[:-len(stop_str)]
-            answers.append({"question_id": line["question_id"], "prompt": line["text"], "text": text.strip(), "naive": dicts[0][i],
-                            "none": dicts[1][i], "unk": dicts[2][i], "answer_id": uuid.uuid4().hex[:22], "model_id": model_id, "metadata": {}})
+        answers = [{"question_id": line["question_id"], "prompt": line["text"], "text": answer_text(decode, got["tokens"][i], eos, stop_str), "naive": dicts[0][i],
+                    "none": dicts[1][i], "unk": dicts[2][i], "answer_id": uuid.uuid4().hex[:22], "model_id": model_id, "metadata": {}}
+                   for i, line in enumerate(qs_all)]
         root = results_root
-        if plan.rank != 0:
+        if run.rank != 0:
             answers_path = root = None                         # rank 0 owns the files
         if answers_path is not None:
-            import json
-            import os
-            os.makedirs(os.path.dirname(os.path.abspath(answers_path)), exist_ok=True)
-            with open(answers_path, "w") as f:
-                for a in answers:
-                    f.write(json.dumps(a) + "\n")
-        out = {"answers": answers, "results": {}, "scores": {}, "batch_invariant": invariant}
+            write_jsonl(answers_path, answers)
+        out = {"answers": answers, "results": {}, "scores": {}, "batch_invariant": run.invariant}
         if gt is not None:
             conv = C.mme_convert(answers, gt)
             out["converted"] = conv
@@ -209,10 +190,9 @@ def run_mme(engine: VddLlavaEngine, questions: Sequence[dict], build_inputs: Cal
                     except (FileNotFoundError, AssertionError):    # a chunk / subset without all 8 task files or with odd line counts
                         out["scores"][name] = None
         return out
-    if sweep is None:
-        return finish(all_rows[0], answers_path, experiment)
-    return {"runs": {s_["tag"]: finish(r_, s_.get("answers_path"), s_.get("experiment", f"{experiment}-{s_['tag']}")) for s_, r_ in zip(settings, all_rows)},
-            "batch_invariant": invariant}
+    return sweep_result(sweep, settings, lambda j, s_: finish(all_rows[j], answers_path if sweep is None else s_.get("answers_path"),
+                                                              experiment if sweep is None else s_.get("experiment", f"{experiment}-{s_['tag']}")),
+                        batch_invariant=run.invariant)
 
 
 def _sweep_settings(args) -> list:
@@ -230,6 +210,27 @@ def _sweep_settings(args) -> list:
     return runs
 
 
+def _parser():
+    import argparse
+    ap = argparse.ArgumentParser()
+    add_common_args(ap, help={"answers_file": "'setting' in the name is replaced per run (default / temp_T / top_p_P / top_k_K)",
+                              "temperature": "default 0.2 (llava) / 1.0 (qwen), as the reference's scripts"})
+    add_script_args(ap, conv_mode="vicuna_v1")
+    ap.add_argument("--arch", choices=("llava", "qwen"), default="llava")
+    ap.add_argument("--model-path", required=True)
+    ap.add_argument("--num_beams", type=int, default=1)
+    ap.add_argument("--max_new_tokens", type=int, default=None, help="default: 128 (llava, run_llava.py:267) / 20 (qwen: the generate call's own value, run_qwen.py:195)")
+    ap.add_argument("--use_dd", action="store_true")
+    ap.add_argument("--use_dd_unk", action="store_true")
+    ap.add_argument("--no-sweep", action="store_true", help="only the 'default' run")
+    ap.add_argument("--gt-root", default=None, help="MME benchmark tree: also convert (naive / none / unk / none_unk) and score")
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--preset", default="llava-1.5-7b")
+    ap.add_argument("--vision-tower", default=None)
+    ap.add_argument("--native-visual", action="store_true", help="--arch qwen: the ViT + resampler on the package's kernels (qwen_visual)")
+    return ap
+
+
 def main(argv=None):
     """python -m llava_align_amd.mme_driver --arch llava|qwen --model-path DIR --image-folder MME_Benchmark --question-file llava_mme.jsonl
     --answers-file OUT-setting.jsonl [--use_dd --use_dd_unk --use_cd --noise_step 500 --cd_alpha 1 --cd_beta 0.1 --temperature T --top_p P
@@ -239,48 +240,17 @@ def main(argv=None):
     --arch llava: a LLaVA-1.5 checkpoint directory (checkpoint.load_llava).  --arch qwen: a Qwen-VL directory loaded through transformers
     (trust_remote_code, the caller's environment must provide what modeling_qwen.py imports) - its ViT + resampler fill the image slots,
     the language model runs natively (hf_adapter.lm_weights_from_hf).  Under torchrun: one rank per GPU, whole images per rank, one gather."""
-    import argparse
     import json
     import os
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=("llava", "qwen"), default="llava")
-    ap.add_argument("--model-path", required=True)
-    ap.add_argument("--model-base", default=None)
-    ap.add_argument("--image-folder", required=True)
-    ap.add_argument("--question-file", required=True)
-    ap.add_argument("--answers-file", required=True, help="'setting' in the name is replaced per run (default / temp_T / top_p_P / top_k_K)")
-    ap.add_argument("--conv-mode", default="vicuna_v1")
-    ap.add_argument("--num-chunks", type=int, default=1)
-    ap.add_argument("--chunk-idx", type=int, default=0)
-    ap.add_argument("--temperature", type=float, default=None, help="default 0.2 (llava) / 1.0 (qwen), as the reference's scripts")
-    ap.add_argument("--top_p", type=float, default=None)
-    ap.add_argument("--top_k", type=int, default=None)
-    ap.add_argument("--num_beams", type=int, default=1)
-    ap.add_argument("--max_new_tokens", type=int, default=None, help="default: 128 (llava, run_llava.py:267) / 20 (qwen: the generate call's own value, run_qwen.py:195)")
-    ap.add_argument("--noise_step", type=int, default=500)
-    ap.add_argument("--use_cd", action="store_true")
-    ap.add_argument("--use_dd", action="store_true")
-    ap.add_argument("--use_dd_unk", action="store_true")
-    ap.add_argument("--cd_alpha", type=float, default=1.0)
-    ap.add_argument("--cd_beta", type=float, default=0.1)
-    ap.add_argument("--no-sweep", action="store_true", help="only the 'default' run")
-    ap.add_argument("--gt-root", default=None, help="MME benchmark tree: also convert (naive / none / unk / none_unk) and score")
-    ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--seed", type=int, default=None)
-    ap.add_argument("--preset", default="llava-1.5-7b")
-    ap.add_argument("--vision-tower", default=None)
-    ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16")
-    ap.add_argument("--native-visual", action="store_true", help="--arch qwen: the ViT + resampler on the package's kernels (qwen_visual)")
-    a = ap.parse_args(argv)
+    a = _parser().parse_args(argv)
     if a.num_beams != 1:
         raise SystemExit("num_beams > 1: the reference patches sample() only (vcd_sample.py:325-326)")
     if a.temperature is None:
         a.temperature = 0.2 if a.arch == "llava" else 1.0
     from . import checkpoint as K
-    from .shard import init_from_env
-    rank, world, device = init_from_env()
+    rank, world, device = shard.init_from_env()
     dtype = getattr(torch, a.dtype)
-    questions = [json.loads(q) for q in open(os.path.expanduser(a.question_file))]
+    questions = read_questions(a.question_file)
     gen_kw = dict(use_dd=a.use_dd, use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta)
     if a.arch == "llava":
         eng, tok, proc = K.load_llava(a.model_path, device, dtype=dtype, vision_tower=a.vision_tower, fallback_preset=a.preset)
@@ -312,10 +282,7 @@ def main(argv=None):
         out_scores[s_["tag"]] = {k: (v and {"Perception": v["Perception"]["total"], "Cognition": v["Cognition"]["total"]}) for k, v in r_["scores"].items()}
         if rank == 0:
             print(json.dumps({"run": s_["tag"], "answers_file": s_["answers_path"], "n_answers": len(r_["answers"]), "scores": out_scores[s_["tag"]]}), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
+    finish_distributed(world)
 
 
 if __name__ == "__main__":

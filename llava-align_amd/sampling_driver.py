@@ -15,8 +15,11 @@ from typing import Callable, List, Optional, Sequence
 
 import torch
 
+from . import shard
+from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, add_script_args, answer_text, chunk_of, eos_set, finish_distributed, load_distinct_images, read_questions,
+                            write_jsonl)
 from .engine import VddLlavaEngine
-from .pope_driver import QUESTION_SUFFIX, cut_at_eos
+from .vcd_add_noise import add_diffusion_noise
 
 
 def llava_v1_user_prompt(user_text: str) -> str:
@@ -37,37 +40,22 @@ def run_sampling(engine: VddLlavaEngine, questions: Sequence[dict], encode: Call
     (shard.ShardPlan), ONE collective gathers the answers, rank 0 writes the file; every rank returns the full result.  Deterministic decodes
     run in batch-invariant mode unless told otherwise (shard.resolve_batch_invariant): same answers on 1 and N ranks, at any in_flight.
     Returns {"answers": [...], "stats": the engine's stats of this rank's chunk}."""
-    import contextlib
-    from . import ops
-    from .shard import ShardPlan, gather_results, resolve_batch_invariant
-    order = sorted(range(len(questions)), key=lambda i: (questions[i]["image"], i))
-    plan = ShardPlan([questions[i]["image"] for i in order], rank, world)
-    mine = [order[p_] for p_ in plan.mine]
-    if generate_kw.get("seed") is not None:
-        generate_kw = dict(generate_kw, seed=int(generate_kw["seed"]) + plan.rank)
-    dev = engine.device
-    cache = {}
-    imgs, ids = [], []
-    for i in mine:
-        q = questions[i]
-        if q["image"] not in cache:
-            cache[q["image"]] = load_image(q["image"]).to(dev)
-        imgs.append(cache[q["image"]])                                   # the SAME tensor for questions about one image: shared features / prefix
-        text = "<image>\n" + q["text"] + (QUESTION_SUFFIX if pope_suffix else "")
-        ids.append(torch.tensor(encode(llava_v1_user_prompt(text))))
-    invariant = resolve_batch_invariant(batch_invariant, plan.world, generate_kw)
+    run = ShardedRun(questions, rank, world, generate_kw, batch_invariant)
+    mine, generate_kw = run.mine, run.generate_kw
+    imgs = load_distinct_images([questions[i]["image"] for i in mine], load_image, engine.device)       # the SAME tensor for questions about one image: shared features / prefix
+    ids = [torch.tensor(encode(llava_v1_user_prompt("<image>\n" + questions[i]["text"] + (QUESTION_SUFFIX if pope_suffix else "")))) for i in mine]
+    pad = pad_token_id if pad_token_id is not None else 0
+    rows = run.rows(engine.device, max_new_tokens, pad_token_id, n_sets=0)
     stats = {}
-    with (ops.batch_invariant() if invariant else contextlib.nullcontext()):
-        if not mine:
-            toks = torch.zeros(0, 1, dtype=torch.long, device=dev)
-        elif generate_kw.get("do_sample", True) is not False:
+    with run.mode():
+        if mine and generate_kw.get("do_sample", True) is not False:
             kw = {k: v for k, v in generate_kw.items() if k != "do_sample"}
             if noise_step is not None:
-                from .vcd_add_noise import add_diffusion_noise
                 kw["images_cd"] = [add_diffusion_noise(im, noise_step) for im in imgs]                 # fresh noise per question (:88-91)
             out = engine.generate_list(ids, imgs, in_flight=in_flight, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, **kw)
-            toks, stats = out.tokens, out.stats
-        else:                       # do_sample=False: greedy_search is not patched - plain arg-max decoding, batch after batch (SURVEY A.3 #5)
+            rows.add(mine, out.tokens)
+            stats = out.stats
+        elif mine:                  # do_sample=False: greedy_search is not patched - plain arg-max decoding, batch after batch (SURVEY A.3 #5)
             parts = []
             for b0 in range(0, len(mine), in_flight):
                 sl = slice(b0, b0 + in_flight)
@@ -75,30 +63,32 @@ def run_sampling(engine: VddLlavaEngine, questions: Sequence[dict], encode: Call
                 parts.append(o.tokens)
                 stats = o.stats
             T = max(p_.shape[1] for p_ in parts)
-            toks = torch.cat([torch.nn.functional.pad(p_, (0, T - p_.shape[1]), value=pad_token_id if pad_token_id is not None else 0) for p_ in parts])
-    width = max_new_tokens
-    pad = pad_token_id if pad_token_id is not None else 0
-    n_tok = torch.full((toks.shape[0],), toks.shape[1], dtype=torch.long, device=dev)
-    res = gather_results(torch.tensor(mine, dtype=torch.long, device=dev), torch.nn.functional.pad(toks, (0, width - toks.shape[1]), value=pad), n_tok, None, None,
-                         len(questions), pad=pad, capacity=plan.capacity, width=width, world=plan.world)
-    if not bool((res["count"] == 1).all().item()):
-        raise RuntimeError(f"result gather: {int((res['count'] != 1).sum())} of {len(questions)} questions were not delivered exactly once")
-    eos_set = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
-    rows, lens = res["tokens"].cpu().tolist(), res["n_tokens"].cpu().tolist()
-    answers = []
-    for i, q in enumerate(questions):
-        text = decode(cut_at_eos(rows[i][:lens[i]], eos_set)).strip()
-        if stop_str and text.endswith(stop_str):
-            text = text[:-len(stop_str)]
-        answers.append({"question_id": q["question_id"], "prompt": q["text"], "text": text.strip(), "model_id": model_id, "image": q["image"], "metadata": {}})
-    if answers_path is not None and plan.rank == 0:
-        import json
-        import os
-        os.makedirs(os.path.dirname(os.path.abspath(answers_path)), exist_ok=True)
-        with open(answers_path, "w") as f:
-            for a in answers:
-                f.write(json.dumps(a) + "\n")
-    return {"answers": answers, "stats": stats, "rank": plan.rank, "world": plan.world, "batch_invariant": invariant}
+            rows.add(mine, torch.cat([torch.nn.functional.pad(p_, (0, T - p_.shape[1]), value=pad) for p_ in parts]))
+    got = run.gather(rows)
+    eos = eos_set(eos_token_id)
+    answers = [{"question_id": q["question_id"], "prompt": q["text"], "text": answer_text(decode, got["tokens"][i], eos, stop_str), "model_id": model_id,
+                "image": q["image"], "metadata": {}} for i, q in enumerate(questions)]
+    if answers_path is not None and run.rank == 0:
+        write_jsonl(answers_path, answers)
+    return {"answers": answers, "stats": stats, "rank": run.rank, "world": run.world, "batch_invariant": run.invariant}
+
+
+def _parser():
+    import argparse
+    ap = argparse.ArgumentParser()
+    add_common_args(ap, image_folder="", temperature=1.0, seed=42)
+    add_script_args(ap)
+    ap.add_argument("--model-path", required=True)
+    ap.add_argument("--use_dd", action="store_true")
+    ap.add_argument("--use_dd_unk", action="store_true")
+    ap.add_argument("--max_new_tokens", type=int, default=1024)
+    ap.add_argument("--in-flight", type=int, default=90)
+    ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--naive", action="store_true", help="experiments/eval/llava_naive.py:39-98: ONE run at --temperature / --top_p / --top_k (greedy at "
+                    "temperature 0), always with the one-word suffix, into --answers-file as given")
+    ap.add_argument("--preset", default="llava-1.5-7b")
+    ap.add_argument("--vision-tower", default=None)
+    return ap
 
 
 def main(argv=None):
@@ -107,45 +97,14 @@ def main(argv=None):
     experiments/eval/sampling/llava_sampling.py:128-195 and its runs - 'default' (temperature 1, no top-p / top-k), then, unless --use_cd,
     temperature 0.05 ... 1.0, top_p 0 ... 1.0, top_k 1 ... 500, each into `answers-file` with 'setting' replaced.  Under torchrun: one rank
     per GPU, whole images per rank, one gather, rank 0 writes the files."""
-    import argparse
     import json
     import os
     import numpy as np
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--model-path", required=True)
-    ap.add_argument("--model-base", default=None)
-    ap.add_argument("--image-folder", default="")
-    ap.add_argument("--question-file", required=True)
-    ap.add_argument("--answers-file", required=True)
-    ap.add_argument("--conv-mode", default="llava_v1")
-    ap.add_argument("--num-chunks", type=int, default=1)
-    ap.add_argument("--chunk-idx", type=int, default=0)
-    ap.add_argument("--noise_step", type=int, default=500)
-    ap.add_argument("--use_cd", action="store_true")
-    ap.add_argument("--cd_alpha", type=float, default=1.0)
-    ap.add_argument("--cd_beta", type=float, default=0.1)
-    ap.add_argument("--use_dd", action="store_true")
-    ap.add_argument("--use_dd_unk", action="store_true")
-    ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--max_new_tokens", type=int, default=1024)
-    ap.add_argument("--in-flight", type=int, default=90)
-    ap.add_argument("--no-sweep", action="store_true")
-    ap.add_argument("--naive", action="store_true", help="experiments/eval/llava_naive.py:39-98: ONE run at --temperature / --top_p / --top_k (greedy at "
-                    "temperature 0), always with the one-word suffix, into --answers-file as given")
-    ap.add_argument("--temperature", type=float, default=1.0)
-    ap.add_argument("--top_p", type=float, default=None)
-    ap.add_argument("--top_k", type=int, default=None)
-    ap.add_argument("--preset", default="llava-1.5-7b")
-    ap.add_argument("--vision-tower", default=None)
-    ap.add_argument("--dtype", choices=("float16", "bfloat16"), default="float16")
-    a = ap.parse_args(argv)
+    a = _parser().parse_args(argv)
     from . import checkpoint as K
-    from .shard import get_chunk, init_from_env
-    rank, world, device = init_from_env()
+    rank, world, device = shard.init_from_env()
     eng, tok, proc = K.load_llava(a.model_path, device, dtype=getattr(torch, a.dtype), vision_tower=a.vision_tower, fallback_preset=a.preset)
-    questions = [json.loads(q) for q in open(os.path.expanduser(a.question_file))]
-    if a.num_chunks > 1:
-        questions = [questions[i] for i in get_chunk(len(questions), a.num_chunks, a.chunk_idx, group=1)]
+    questions = chunk_of(read_questions(a.question_file), a)
     runs = [("default", 1.0, None, None)]
     if a.naive:
         runs = [(None, a.temperature, a.top_p, a.top_k)]
@@ -165,10 +124,7 @@ def main(argv=None):
                            cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, temperature=temp if temp > 0 else 1.0, top_p=top_p, top_k=top_k, seed=a.seed, **greedy)
         if rank == 0:
             print(json.dumps({"run": tag or "naive", "answers_file": path, "n_answers": len(res["answers"]), "stats": {k: v for k, v in res["stats"].items() if not hasattr(v, "__len__") or isinstance(v, str)}}), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
+    finish_distributed(world)
 
 
 if __name__ == "__main__":
