@@ -250,6 +250,40 @@ int vdd_decode_attention(const void* q, const void* k_cache, const void* v_cache
                          int64_t prefix_stride, int prefix_tmax, int max_len, float scale, int dtype, void* hip_stream);
 int64_t vdd_decode_attention_workspace_bytes(int M, int H, int D, int max_len);
 
+/* ---- paged own-KV pool (engine.generate_list(paged_kv=True)): own-KV memory follows the tokens really generated.
+ * Pools, one pair per layer: k_pages / v_pages [n_pages, Hkv, VDD_KV_PAGE, D], dense (page_stride = Hkv * VDD_KV_PAGE * D elements).
+ * A page holds VDD_KV_PAGE consecutive own tokens of ONE own slot, for all KV heads.
+ * page_table: int32 [n_slots, max_pages_per_slot], indexed by the OWN-SLOT id the kernels already get (slot[row], rows[m].slot) -
+ * not by the row's place in the call - so a smaller step over surviving slots reads the same table.  Own token i of slot s lives in
+ * page page_table[s][i / VDD_KV_PAGE] at index i % VDD_KV_PAGE; -1 = no page.
+ * Nothing the table or the row arrays hold can make a kernel touch memory outside the pools and the table: an entry < 0 or
+ * >= n_pages, a slot outside [0, n_slots) and an own index outside [0, max_pages_per_slot * VDD_KV_PAGE) all count as "no page" -
+ * a store is skipped, a key is read from page 0 and left out of the softmax (a wrong number, never a fault).  The entries refuse
+ * a null pool / table, n_pages, n_slots or max_pages_per_slot < 1 and a page_stride other than the dense one before any launch. */
+#define VDD_KV_PAGE 16
+
+/* vdd_rope_kv_write with the K / V destination looked up in the page table: slot[row] indexes the table, cpos[row] is the own
+ * index.  q_out is bit-identical to vdd_rope_kv_write's; a row without a page for cpos[row] stores no K / V. */
+int vdd_rope_kv_write_paged(const void* qkv, const int* pos, const int* cpos, const int* slot, const float* cos_sin, void* q_out,
+                            void* k_pages, void* v_pages, const int32_t* page_table, int M, int Hq, int Hkv, int D, int64_t page_stride,
+                            int n_pages, int n_slots, int max_pages_per_slot, int dtype, void* hip_stream);
+
+/* vdd_decode_attention with the own range [plen, len) of every row read through the page table (own index = key - plen); the prefix
+ * range comes from the row-major prefix pool as there.  Same 64-key chunks over the absolute key index, same lane-group-to-key map,
+ * same online-softmax order, same combine: the output is bit-identical to vdd_decode_attention over contiguous slots holding the
+ * same K / V.  Workspace: vdd_decode_attention_workspace_bytes(M, H, D, max_len). */
+int vdd_decode_attention_paged(const void* q, const void* k_pages, const void* v_pages, const int32_t* page_table, const void* k_prefix,
+                               const void* v_prefix, const int32_t* rows, void* out, void* workspace, int M, int H, int Hkv, int D,
+                               int64_t page_stride, int n_pages, int n_slots, int max_pages_per_slot, int64_t prefix_stride,
+                               int prefix_tmax, int max_len, float scale, int dtype, void* hip_stream);
+
+/* Contiguous own slots -> pages, one layer per call: the first n_tok[r] (<= max_tok) tokens of slot slots[r] of the contiguous
+ * pools k_own / v_own [n_slots, Hkv, t_max, D] (slot stride in elements) are copied into the pages of that slot, r < M.  The
+ * admission prefill writes a question's suffix into such a staging slot; no prefill kernel needs a paged form. */
+int vdd_kv_pages_scatter(const void* k_own, const void* v_own, void* k_pages, void* v_pages, const int32_t* page_table,
+                         const int32_t* slots, const int32_t* n_tok, int M, int max_tok, int Hkv, int D, int64_t slot_stride, int t_max,
+                         int64_t page_stride, int n_pages, int n_slots, int max_pages_per_slot, int dtype, void* hip_stream);
+
 /* Small-M decode attention with RoPE, the KV-cache write and the chunk merge fused into ONE launch (the reference's own
  * operating point: one question = 2-3 branch rows per step, where the step is launch-latency bound).  `qkv` is the
  * un-rotated projection [M, (H + 2 Hkv) * D]; the new token's K/V are rotated in registers, stored at index cpos[row]

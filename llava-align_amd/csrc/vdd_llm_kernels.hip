@@ -157,14 +157,13 @@ __global__ void __launch_bounds__(256) rmsnorm_kernel(const uint16_t* __restrict
 // qkv: [M, (Hq + 2 Hkv) * D] (q | k | v).  One block per row, one 16-lane group per head
 // chunk.  rotate_half pairing (HF Llama): (i, i + D/2).  cos/sin table: fp32 [max_pos, D/2].
 // K/V go to cache[slot][kv_head][pos][D].
-__global__ void __launch_bounds__(256) rope_kv_kernel(const uint16_t* __restrict__ qkv, const int* __restrict__ pos,
-                                                      const int* __restrict__ cpos, const int* __restrict__ slot,
-                                                      const float* __restrict__ cs_table,
-                                                      uint16_t* __restrict__ q_out, uint16_t* __restrict__ k_cache,
-                                                      uint16_t* __restrict__ v_cache, int Hq, int Hkv, int D,
-                                                      long long slot_stride, int t_max, int stream) {
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const int p = pos[row], s = slot[row], cp = cpos[row];     // rotary position vs index inside the cache slot
+// The row's work, shared by the contiguous and the paged kernel: p = rotary position; (s, cp) = cache slot and index inside it
+// (a page and the index inside the page for the paged pool); write_kv = false (block-uniform) leaves the caches alone.
+__device__ __forceinline__ void rope_kv_row(const uint16_t* __restrict__ qkv, const float* __restrict__ cs_table,
+                                            uint16_t* __restrict__ q_out, uint16_t* __restrict__ k_cache,
+                                            uint16_t* __restrict__ v_cache, int Hq, int Hkv, int D, long long slot_stride,
+                                            int t_max, int stream, int row, int p, int s, int cp, bool write_kv) {
+    const int tid = threadIdx.x;
     const int half = D / 2, h8 = half / 8;                      // a work item = 8 consecutive pairs (i, i + D/2) of one head
     const uint16_t* src = qkv + (size_t)row * (size_t)((Hq + 2 * Hkv) * D);
     const float* cs = cs_table + (size_t)p * half * 2;
@@ -204,11 +203,13 @@ __global__ void __launch_bounds__(256) rope_kv_kernel(const uint16_t* __restrict
                 rot(a4[k].w, b4[k].w, c[k][3].x, c[k][3].y, c[k][3].z, c[k][3].w, r0.w, r1.w);
                 uint16_t* dst = is_k ? k_cache + (size_t)s * slot_stride + ((size_t)(head - Hq) * t_max + cp) * D
                                      : q_out + (size_t)row * Hq * D + (size_t)head * D;
+                if (is_k && !write_kv) continue;
                 if (is_k && stream) { st_stream(dst + pi, r0); st_stream(dst + pi + half, r1); }
                 else { *reinterpret_cast<uint4*>(dst + pi) = r0; *reinterpret_cast<uint4*>(dst + pi + half) = r1; }
             }
         }
     }
+    if (!write_kv) return;
     const uint16_t* vsrc = src + (size_t)(Hq + Hkv) * D;
     const int n_v = Hkv * D / 8;
     for (int i0 = tid; i0 < n_v; i0 += 256 * IT) {
@@ -227,6 +228,61 @@ __global__ void __launch_bounds__(256) rope_kv_kernel(const uint16_t* __restrict
                 if (stream) st_stream(vd, vv[k]); else *reinterpret_cast<uint4*>(vd) = vv[k];
             }
         }
+    }
+}
+
+__global__ void __launch_bounds__(256) rope_kv_kernel(const uint16_t* __restrict__ qkv, const int* __restrict__ pos,
+                                                      const int* __restrict__ cpos, const int* __restrict__ slot,
+                                                      const float* __restrict__ cs_table,
+                                                      uint16_t* __restrict__ q_out, uint16_t* __restrict__ k_cache,
+                                                      uint16_t* __restrict__ v_cache, int Hq, int Hkv, int D,
+                                                      long long slot_stride, int t_max, int stream) {
+    const int row = blockIdx.x;
+    rope_kv_row(qkv, cs_table, q_out, k_cache, v_cache, Hq, Hkv, D, slot_stride, t_max, stream, row, pos[row], slot[row], cpos[row], true);
+}
+
+// Paged own-KV pool (engine.generate_list(paged_kv=True)): pools [n_pages, Hkv, KV_PAGE, D]; own token i of own slot s lives in page
+// table[s][i / KV_PAGE] at index i % KV_PAGE.  A page is a KV_PAGE-token cache slot, so the row's work is rope_kv_row with
+// (slot, index) = (page, i % KV_PAGE).  No page (entry < 0), or anything out of range: q is still rotated, K / V are not stored.
+constexpr int KV_PAGE = VDD_KV_PAGE;
+struct PageTable { const int* table; int n_slots, max_pages, n_pages; };
+// page of own token i of slot s, or -1
+__device__ __forceinline__ int page_of(const PageTable& pt, int s, int i) {
+    const int pi = i / KV_PAGE;
+    if (s < 0 || s >= pt.n_slots || i < 0 || pi >= pt.max_pages) return -1;
+    const int pg = pt.table[(size_t)s * pt.max_pages + pi];
+    return pg < pt.n_pages ? pg : -1;
+}
+
+__global__ void __launch_bounds__(256) rope_kv_paged_kernel(const uint16_t* __restrict__ qkv, const int* __restrict__ pos,
+                                                            const int* __restrict__ cpos, const int* __restrict__ slot,
+                                                            const float* __restrict__ cs_table, uint16_t* __restrict__ q_out,
+                                                            uint16_t* __restrict__ k_pages, uint16_t* __restrict__ v_pages,
+                                                            PageTable pt, int Hq, int Hkv, int D, int stream) {
+    const int row = blockIdx.x, cp = cpos[row];
+    const int pg = page_of(pt, slot[row], cp);
+    rope_kv_row(qkv, cs_table, q_out, k_pages, v_pages, Hq, Hkv, D, (long long)Hkv * KV_PAGE * D, KV_PAGE, stream, row, pos[row],
+                pg < 0 ? 0 : pg, cp & (KV_PAGE - 1), pg >= 0);
+}
+
+// Contiguous own slots -> pages (the admission prefill writes a question's suffix K / V into a short contiguous staging slot):
+// block (i, r) copies own token i < n_tok[r] of slot slots[r], all KV heads, K and V, 16 bytes per lane.
+__global__ void __launch_bounds__(256) kv_pages_scatter_kernel(const uint16_t* __restrict__ k_own, const uint16_t* __restrict__ v_own,
+                                                               uint16_t* __restrict__ k_pages, uint16_t* __restrict__ v_pages,
+                                                               PageTable pt, const int* __restrict__ slots,
+                                                               const int* __restrict__ n_tok, int Hkv, int D, long long slot_stride,
+                                                               int t_max, int n_own) {
+    const int i = blockIdx.x, r = blockIdx.y, s = slots[r];
+    if (i >= n_tok[r] || i >= t_max || s < 0 || s >= n_own) return;
+    const int pg = page_of(pt, s, i);
+    if (pg < 0) return;
+    const int d8 = D / 8;
+    for (int e = threadIdx.x; e < Hkv * d8; e += 256) {
+        const int head = e / d8, dd = (e % d8) * 8;
+        const size_t src = (size_t)s * slot_stride + ((size_t)head * t_max + i) * D + dd;
+        const size_t dst = ((size_t)pg * Hkv + head) * KV_PAGE * D + (size_t)(i & (KV_PAGE - 1)) * D + dd;
+        *reinterpret_cast<uint4*>(k_pages + dst) = *reinterpret_cast<const uint4*>(k_own + src);
+        *reinterpret_cast<uint4*>(v_pages + dst) = *reinterpret_cast<const uint4*>(v_own + src);
     }
 }
 
@@ -836,13 +892,48 @@ constexpr int ATT_CH = 64;
 // store of one is 16-byte aligned (520-byte records cost the prefix pass 10 us of partial-line write traffic: tools/probes/hbm_stream_probe.hip)
 constexpr int ATT_PS = 128 + 4;
 
-template <int D>   // head dim 128
-__global__ void __launch_bounds__(256) decode_attn_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
-                                                          const uint16_t* __restrict__ vc, const uint16_t* __restrict__ kpre,
-                                                          const uint16_t* __restrict__ vpre, const AttnRow* __restrict__ rows,
-                                                          float* __restrict__ ws, int H, int Hkv, long long slot_stride,
-                                                          int t_max, long long pre_stride, int pre_tmax, float scale, int nchunk,
-                                                          int own_only, int chunk_base) {
+// Where the own keys of a row live.  `at(ar, kvh, j, Hkv)` is called once per wave and returns the wave's view: k(tt) / v(tt) = the
+// address of the lane's 8 dims of own key tt (absolute index, plen <= tt < len; any tt must give a VALID address: the loop loads
+// before it tests), ok(tt) = whether the key exists.
+template <int D>
+struct OwnContiguous {      // compact slots [n_slots, Hkv, t_max, D]: token tt at index tt - plen of slot ar.slot
+    const uint16_t *kc, *vc; long long slot_stride; int t_max;
+    struct View {
+        const uint16_t *kb, *vb;
+        __device__ __forceinline__ const uint16_t* k(int tt) const { return kb + (size_t)tt * D; }
+        __device__ __forceinline__ const uint16_t* v(int tt) const { return vb + (size_t)tt * D; }
+        __device__ __forceinline__ bool ok(int) const { return true; }
+    };
+    __device__ __forceinline__ View at(const AttnRow& ar, int kvh, int j, int) const {
+        const size_t hoff = (size_t)kvh * t_max * D + j * 8;
+        return View{kc + (size_t)ar.slot * slot_stride + hoff - (size_t)ar.plen * D, vc + (size_t)ar.slot * slot_stride + hoff - (size_t)ar.plen * D};
+    }
+};
+template <int D>
+struct OwnPaged {           // page pools [n_pages, Hkv, KV_PAGE, D] behind the page table: ONE table entry per key (a table row is a few dozen
+    const uint16_t *kp, *vp; PageTable pt;      // ints shared by all waves of the row: it stays in cache).  A key without a page is read
+    struct View {                               // from page 0 and left out of the softmax.
+        const uint16_t *kp, *vp; PageTable pt; int slot, plen; size_t hoff; long long page_stride;
+        __device__ __forceinline__ size_t off(int tt) const {
+            const int i = tt > plen ? tt - plen : 0, pg = page_of(pt, slot, i);
+            return (size_t)(pg < 0 ? 0 : pg) * page_stride + hoff + (size_t)(i & (KV_PAGE - 1)) * D;
+        }
+        __device__ __forceinline__ const uint16_t* k(int tt) const { return kp + off(tt); }
+        __device__ __forceinline__ const uint16_t* v(int tt) const { return vp + off(tt); }
+        __device__ __forceinline__ bool ok(int tt) const { return tt < plen || page_of(pt, slot, tt - plen) >= 0; }
+    };
+    __device__ __forceinline__ View at(const AttnRow& ar, int kvh, int j, int Hkv) const {
+        return View{kp, vp, pt, ar.slot, ar.plen, (size_t)kvh * KV_PAGE * D + j * 8, (long long)Hkv * KV_PAGE * D};
+    }
+};
+
+// The work of one (row, head, chunk) wave - ONE body for the contiguous and the paged kernel, so that both walk the same 64-key
+// chunks with the same lane-group-to-key map and the same online-softmax order: equal K / V give equal bits.
+template <int D, class Own>   // head dim 128
+__device__ __forceinline__ void decode_attn_chunk(const uint16_t* __restrict__ q, const Own pool, const uint16_t* __restrict__ kpre,
+                                                  const uint16_t* __restrict__ vpre, const AttnRow* __restrict__ rows, float* __restrict__ ws,
+                                                  int H, int Hkv, long long pre_stride, int pre_tmax, float scale, int nchunk,
+                                                  int own_only, int chunk_base) {
     static_assert(D == 128, "lane map assumes 16 lanes x 8 dims");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int head = blockIdx.x * 4 + wave, row = blockIdx.y, chunk = blockIdx.z;
@@ -858,30 +949,31 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const uint16_t* __rest
     }
     const int kvh = head / (H / Hkv);
     const uint4 qv = *reinterpret_cast<const uint4*>(q + ((size_t)row * H + head) * D + j * 8);
-    // own pool stores token t at index t - plen (compact slots); the prefix pool at index t
-    const size_t hoff = (size_t)kvh * t_max * D + j * 8, poff = (size_t)kvh * pre_tmax * D + j * 8;
-    const uint16_t* k_own = kc + (size_t)ar.slot * slot_stride + hoff - (size_t)ar.plen * D;
-    const uint16_t* v_own = vc + (size_t)ar.slot * slot_stride + hoff - (size_t)ar.plen * D;
+    // own pool stores token t at index t - plen (compact slots or pages); the prefix pool at index t
+    const size_t poff = (size_t)kvh * pre_tmax * D + j * 8;
+    const auto own = pool.at(ar, kvh, j, Hkv);
     const uint16_t* k_pre = kpre + (size_t)ar.pslot * pre_stride + poff;
     const uint16_t* v_pre = vpre + (size_t)ar.pslot * pre_stride + poff;
     float m = -INFINITY, l = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     constexpr int U = 4;
     for (int t0 = k0 + g; t0 < k1; t0 += 4 * U) {
         uint4 kv[U], vv[U];
+        bool there[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int t = t0 + 4 * u;
             const int tt = t < k1 ? t : k1 - 1;
             const bool pre = tt < ar.plen;
-            kv[u] = ld_stream((pre ? k_pre : k_own) + (size_t)tt * D);          // each K / V row is read by one wave of the launch
-            vv[u] = ld_stream((pre ? v_pre : v_own) + (size_t)tt * D);
+            kv[u] = ld_stream(pre ? k_pre + (size_t)tt * D : own.k(tt));        // each K / V row is read by one wave of the launch
+            vv[u] = ld_stream(pre ? v_pre + (size_t)tt * D : own.v(tt));
+            there[u] = t < k1 && own.ok(tt);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             float s = dot8(qv, kv[u]);
             s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4); s += __shfl_xor(s, 8);
             s *= scale;
-            if (t0 + 4 * u < k1) ATT_ONLINE_STEP(s, vv[u], m, l, acc);
+            if (there[u]) ATT_ONLINE_STEP(s, vv[u], m, l, acc);
         }
     }
     // merge the 4 lane groups (xor 16, 32)
@@ -900,6 +992,26 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const uint16_t* __rest
         *reinterpret_cast<float4*>(wsp + j * 8 + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
         if (j == 0) { wsp[D] = m; wsp[D + 1] = l; }
     }
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) decode_attn_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
+                                                          const uint16_t* __restrict__ vc, const uint16_t* __restrict__ kpre,
+                                                          const uint16_t* __restrict__ vpre, const AttnRow* __restrict__ rows,
+                                                          float* __restrict__ ws, int H, int Hkv, long long slot_stride,
+                                                          int t_max, long long pre_stride, int pre_tmax, float scale, int nchunk,
+                                                          int own_only, int chunk_base) {
+    decode_attn_chunk<D>(q, OwnContiguous<D>{kc, vc, slot_stride, t_max}, kpre, vpre, rows, ws, H, Hkv, pre_stride, pre_tmax, scale, nchunk,
+                         own_only, chunk_base);
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) decode_attn_paged_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k_pages,
+                                                                const uint16_t* __restrict__ v_pages, PageTable pt,
+                                                                const uint16_t* __restrict__ kpre, const uint16_t* __restrict__ vpre,
+                                                                const AttnRow* __restrict__ rows, float* __restrict__ ws, int H, int Hkv,
+                                                                long long pre_stride, int pre_tmax, float scale, int nchunk) {
+    decode_attn_chunk<D>(q, OwnPaged<D>{k_pages, v_pages, pt}, kpre, vpre, rows, ws, H, Hkv, pre_stride, pre_tmax, scale, nchunk, 0, 0);
 }
 
 // Grouped mode, short own ranges (a question's own prompt tokens + what it generated so far: <= 256 keys): ONE wave per
@@ -1419,6 +1531,37 @@ VDD_HIDDEN int VDD_IMPL(vdd_rope_kv_write)(const void* qkv, const int* pos, cons
     return ok(hipSuccess);
 }
 
+// what the three paged entries check before any launch: a dense page pool and a table that can be indexed
+static bool paged_args_ok(const void* k_pages, const void* v_pages, const int32_t* page_table, int Hkv, int D, int64_t page_stride, int n_pages,
+                          int n_slots, int max_pages_per_slot) {
+    return k_pages && v_pages && page_table && Hkv > 0 && D > 0 && D % 8 == 0 && n_pages > 0 && n_slots > 0 && max_pages_per_slot > 0 &&
+           page_stride == (int64_t)Hkv * KV_PAGE * D;
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_rope_kv_write_paged)(const void* qkv, const int* pos, const int* cpos, const int* slot, const float* cos_sin, void* q_out,
+                            void* k_pages, void* v_pages, const int32_t* page_table, int M, int Hq, int Hkv, int D, int64_t page_stride,
+                            int n_pages, int n_slots, int max_pages_per_slot, void* stream) {
+    if (M <= 0) return VDD_OK;
+    if (!qkv || !pos || !cpos || !slot || !cos_sin || !q_out || D % 16 != 0 ||
+        !paged_args_ok(k_pages, v_pages, page_table, Hkv, D, page_stride, n_pages, n_slots, max_pages_per_slot)) return VDD_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(rope_kv_paged_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)qkv, pos, cpos, slot, cos_sin,
+                       (uint16_t*)q_out, (uint16_t*)k_pages, (uint16_t*)v_pages, PageTable{page_table, n_slots, max_pages_per_slot, n_pages},
+                       Hq, Hkv, D, M <= 8192 ? 1 : 0);
+    return ok(hipSuccess);
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_kv_pages_scatter)(const void* k_own, const void* v_own, void* k_pages, void* v_pages, const int32_t* page_table,
+                         const int32_t* slots, const int32_t* n_tok, int M, int max_tok, int Hkv, int D, int64_t slot_stride, int t_max,
+                         int64_t page_stride, int n_pages, int n_slots, int max_pages_per_slot, void* stream) {
+    if (M <= 0 || max_tok <= 0) return VDD_OK;
+    if (!k_own || !v_own || !slots || !n_tok || M > 65535 || t_max <= 0 || slot_stride < (int64_t)Hkv * t_max * D ||
+        !paged_args_ok(k_pages, v_pages, page_table, Hkv, D, page_stride, n_pages, n_slots, max_pages_per_slot)) return VDD_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(kv_pages_scatter_kernel, dim3(max_tok < t_max ? max_tok : t_max, M), dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t*)k_own, (const uint16_t*)v_own, (uint16_t*)k_pages, (uint16_t*)v_pages,
+                       PageTable{page_table, n_slots, max_pages_per_slot, n_pages}, slots, n_tok, Hkv, D, (long long)slot_stride, t_max, n_slots);
+    return ok(hipSuccess);
+}
+
 VDD_HIDDEN int VDD_IMPL(vdd_silu_mul)(const void* gate_up, void* out, int64_t M, int F, void* stream) {
     if (M <= 0) return VDD_OK;
     if (!gate_up || !out || F % 8 != 0) return VDD_ERR_INVALID_ARG;
@@ -1563,6 +1706,24 @@ VDD_HIDDEN int VDD_IMPL(vdd_decode_attention)(const void* q, const void* k_cache
                        (const uint16_t*)k_cache, (const uint16_t*)v_cache, (const uint16_t*)k_prefix, (const uint16_t*)v_prefix,
                        (const AttnRow*)rows, (float*)workspace, H, Hkv, (long long)slot_stride, t_max, (long long)prefix_stride,
                        prefix_tmax, scale, nchunk, 0, 0);
+    hipLaunchKernelGGL(decode_attn_combine_kernel<128>, dim3((H + 3) / 4, M), dim3(256), 0, st, (const float*)workspace,
+                       (const AttnRow*)rows, (uint16_t*)out, H, nchunk, 0, ATT_CH);
+    return ok(hipSuccess);
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_decode_attention_paged)(const void* q, const void* k_pages, const void* v_pages, const int32_t* page_table,
+                               const void* k_prefix, const void* v_prefix, const int32_t* rows, void* out, void* workspace, int M, int H,
+                               int Hkv, int D, int64_t page_stride, int n_pages, int n_slots, int max_pages_per_slot, int64_t prefix_stride,
+                               int prefix_tmax, int max_len, float scale, void* stream) {
+    if (M <= 0) return VDD_OK;
+    if (!q || !k_prefix || !v_prefix || !rows || !out || !workspace || D != 128 || Hkv <= 0 || H % Hkv != 0 || max_len <= 0 ||
+        !paged_args_ok(k_pages, v_pages, page_table, Hkv, D, page_stride, n_pages, n_slots, max_pages_per_slot)) return VDD_ERR_INVALID_ARG;
+    const int nchunk = (max_len + ATT_CH - 1) / ATT_CH;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(decode_attn_paged_kernel<128>, dim3((H + 3) / 4, M, nchunk), dim3(256), 0, st, (const uint16_t*)q,
+                       (const uint16_t*)k_pages, (const uint16_t*)v_pages, PageTable{page_table, n_slots, max_pages_per_slot, n_pages},
+                       (const uint16_t*)k_prefix, (const uint16_t*)v_prefix, (const AttnRow*)rows, (float*)workspace, H, Hkv,
+                       (long long)prefix_stride, prefix_tmax, scale, nchunk);
     hipLaunchKernelGGL(decode_attn_combine_kernel<128>, dim3((H + 3) / 4, M), dim3(256), 0, st, (const float*)workspace,
                        (const AttnRow*)rows, (uint16_t*)out, H, nchunk, 0, ATT_CH);
     return ok(hipSuccess);

@@ -27,6 +27,16 @@ VDD_MODEL_FN(vdd_rope_kv_write,
              VDD_P(const void* qkv, const int* pos, const int* cpos, const int* slot, const float* cos_sin, void* q_out, void* k_cache, void* v_cache,
                    int M, int Hq, int Hkv, int D, int64_t slot_stride, int t_max),
              VDD_P(qkv, pos, cpos, slot, cos_sin, q_out, k_cache, v_cache, M, Hq, Hkv, D, slot_stride, t_max))
+VDD_MODEL_FN(vdd_rope_kv_write_paged,
+             VDD_P(const void* qkv, const int* pos, const int* cpos, const int* slot, const float* cos_sin, void* q_out, void* k_pages, void* v_pages,
+                   const int32_t* page_table, int M, int Hq, int Hkv, int D, int64_t page_stride, int n_pages, int n_slots, int max_pages_per_slot),
+             VDD_P(qkv, pos, cpos, slot, cos_sin, q_out, k_pages, v_pages, page_table, M, Hq, Hkv, D, page_stride, n_pages, n_slots, max_pages_per_slot))
+VDD_MODEL_FN(vdd_kv_pages_scatter,
+             VDD_P(const void* k_own, const void* v_own, void* k_pages, void* v_pages, const int32_t* page_table, const int32_t* slots,
+                   const int32_t* n_tok, int M, int max_tok, int Hkv, int D, int64_t slot_stride, int t_max, int64_t page_stride, int n_pages,
+                   int n_slots, int max_pages_per_slot),
+             VDD_P(k_own, v_own, k_pages, v_pages, page_table, slots, n_tok, M, max_tok, Hkv, D, slot_stride, t_max, page_stride, n_pages, n_slots,
+                   max_pages_per_slot))
 VDD_MODEL_FN(vdd_silu_mul, VDD_P(const void* gate_up, void* out, int64_t M, int F), VDD_P(gate_up, out, M, F))
 VDD_MODEL_FN(vdd_embed, VDD_P(const int64_t* ids, const void* table, void* out, int M, int d, int vocab), VDD_P(ids, table, out, M, d, vocab))
 VDD_MODEL_FN(vdd_embed_scatter, VDD_P(const int32_t* ids, const int32_t* rows, const void* table, void* out, int M, int d, int vocab),
@@ -54,6 +64,12 @@ VDD_MODEL_FN(vdd_decode_attention,
                    void* workspace, int M, int H, int Hkv, int D, int64_t slot_stride, int t_max, int64_t prefix_stride, int prefix_tmax, int max_len,
                    float scale),
              VDD_P(q, k_cache, v_cache, k_prefix, v_prefix, rows, out, workspace, M, H, Hkv, D, slot_stride, t_max, prefix_stride, prefix_tmax, max_len, scale))
+VDD_MODEL_FN(vdd_decode_attention_paged,
+             VDD_P(const void* q, const void* k_pages, const void* v_pages, const int32_t* page_table, const void* k_prefix, const void* v_prefix,
+                   const int32_t* rows, void* out, void* workspace, int M, int H, int Hkv, int D, int64_t page_stride, int n_pages, int n_slots,
+                   int max_pages_per_slot, int64_t prefix_stride, int prefix_tmax, int max_len, float scale),
+             VDD_P(q, k_pages, v_pages, page_table, k_prefix, v_prefix, rows, out, workspace, M, H, Hkv, D, page_stride, n_pages, n_slots,
+                   max_pages_per_slot, prefix_stride, prefix_tmax, max_len, scale))
 VDD_MODEL_FN(vdd_decode_attention_fused,
              VDD_P(const void* qkv, const int32_t* pos, const int32_t* cpos, const int32_t* slot, const float* cos_sin, void* k_cache, void* v_cache,
                    const void* k_prefix, const void* v_prefix, const int32_t* rows, void* out, int M, int H, int Hkv, int D, int64_t slot_stride, int t_max,

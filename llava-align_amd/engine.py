@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .paged_kv import PAGE, ListPager, pages_for
 from .sampling import WarpSpec, contrast_sample
 
 IMAGE_TOKEN_INDEX = -200   # experiments/llava/constants.py:8
@@ -351,11 +352,22 @@ class KVCache:
             and converts the scratch into `pfrag[i]` before the next layer overwrites it.  Round 3 kept both forms for every layer:
             129 slots x 4 x 168 MB = 87 GB of the 189 GB peak of a 768-question batch, half of it read once;
     `pre`   (frag_only=False: few rows in flight / nothing worth grouping - the decode kernels read row-major prefixes) per-layer
-            row-major pools [n_pre, n_kv_heads, t_pre, head_dim], token t at index t, and no fragment image at all."""
+            row-major pools [n_pre, n_kv_heads, t_pre, head_dim], token t at index t, and no fragment image at all.
+    Paged form (n_pages > 0, generate_list(paged_kv=True); row-major prefixes): the decode steps keep their own tokens in page pools
+    `pk` / `pv` [n_pages, n_kv_heads, PAGE, head_dim] behind `page_table` (int32 [n_own, max_pages], indexed by own-slot id, static:
+    the captured steps read it, the host rewrites it between replays); `own` shrinks to a staging area of t_own = the longest
+    suffix, which the admission prefill writes and vdd_kv_pages_scatter empties into the pages."""
 
-    def __init__(self, lm: LMConfig, n_pre: int, t_pre: int, n_own: int, t_own: int, device, dtype=torch.bfloat16, frag_only: bool = False):
+    def __init__(self, lm: LMConfig, n_pre: int, t_pre: int, n_own: int, t_own: int, device, dtype=torch.bfloat16, frag_only: bool = False,
+                 n_pages: int = 0, max_pages: int = 0):
         self.dtype, self.frag_only = dtype, frag_only
         self.n_pre, self.t_pre, self.n_own, self.t_own = n_pre, t_pre, n_own, t_own
+        self.n_pages, self.max_pages = n_pages, max_pages
+        self.pk = self.pv = self.page_table = None
+        if n_pages:
+            self.pk = [torch.empty((n_pages, lm.n_kv_heads, PAGE, lm.head_dim), dtype=dtype, device=device) for _ in range(lm.n_layers)]
+            self.pv = [torch.empty((n_pages, lm.n_kv_heads, PAGE, lm.head_dim), dtype=dtype, device=device) for _ in range(lm.n_layers)]
+            self.page_table = torch.full((max(n_own, 1), max_pages), -1, dtype=torch.int32, device=device)
         mk1 = lambda n, t: torch.empty((max(n, 1), lm.n_kv_heads, t, lm.head_dim), dtype=dtype, device=device)
         mk = lambda n, t: [mk1(n, t) for _ in range(lm.n_layers)]
         if frag_only:
@@ -368,13 +380,19 @@ class KVCache:
         self.ko, self.vo = mk(n_own, t_own), mk(n_own, t_own)
 
     @staticmethod
-    def bytes_needed(lm: LMConfig, n_pre, t_pre, n_own, t_own, dtype, frag_only) -> int:
+    def bytes_needed(lm: LMConfig, n_pre, t_pre, n_own, t_own, dtype, frag_only, n_pages=0) -> int:
         per = lm.n_kv_heads * lm.head_dim * (2 if dtype in (torch.bfloat16, torch.float16) else 4)
         pre = max(n_pre, 1) * t_pre * per * 2
-        return lm.n_layers * max(n_own, 1) * t_own * per * 2 + (lm.n_layers * pre + pre if frag_only else lm.n_layers * pre)
+        return (lm.n_layers * (max(n_own, 1) * t_own + n_pages * PAGE) * per * 2
+                + (lm.n_layers * pre + pre if frag_only else lm.n_layers * pre))
 
-    def fits(self, n_pre, t_pre, n_own, t_own, frag_only):
-        return (frag_only == self.frag_only and n_pre <= self.n_pre and t_pre <= self.t_pre and n_own <= self.n_own and t_own <= self.t_own)
+    def fits(self, n_pre, t_pre, n_own, t_own, frag_only, n_pages=0, max_pages=0):
+        return (frag_only == self.frag_only and n_pre <= self.n_pre and t_pre <= self.t_pre and n_own <= self.n_own and t_own <= self.t_own
+                and bool(n_pages) == bool(self.n_pages) and n_pages <= self.n_pages and max_pages <= self.max_pages)
+
+    @property
+    def own_span(self) -> int:              # own keys a row can attend: what the split-KV workspace and its chunk count are sized for
+        return self.max_pages * PAGE if self.n_pages else self.t_own
 
     def repack_own(self, keep_slots: torch.Tensor, live_len: int, t_own: int):
         """Row retirement / growth of the own pools: keep the slots `keep_slots` (int64 device tensor, in their new order: old slot
@@ -396,7 +414,7 @@ class KVCache:
 
     def nbytes(self):
         seen, total = set(), 0
-        for pool in (self.kp, self.vp, self.pfrag, self.ko, self.vo):
+        for pool in (self.kp, self.vp, self.pfrag, self.ko, self.vo, self.pk or [], self.pv or []):
             for t in pool:
                 if t is not None and t.data_ptr() not in seen:
                     seen.add(t.data_ptr())
@@ -585,6 +603,10 @@ class LanguageModel:
             raise ValueError("decode_step: a frag_only KVCache decodes through the grouped attention only (pass `grouping`)")
         resid = ops.embed(tokens, t["embed"])
         M = tokens.shape[0]
+        if kv.n_pages:                     # paged own KV: every row count takes rope_kv_write_paged + decode_attention_paged
+            if grouping is not None:
+                raise ValueError("decode_step: the grouped attention has no paged form")
+            return self._decode_layers(resid, pos, cpos, slot, attn_rows, kv, None, workspace)
         if self.fuse_norms and grouping is None and M <= ops.FUSED_ATTN_MAX_M and D == 128 and c.ffn % 128 == 0 and c.n_layers > 0:
             # few rows: the norm-fused five-launch layer or the seven-launch layer, whichever makes THIS step faster - measured once per
             # (rows, width, dtype) on the real step (both forms write the same K / V and leave the runner's state alone), then persisted
@@ -610,7 +632,11 @@ class LanguageModel:
             else:
                 a = ops.rmsnorm(resid, t[p + "ln1"], c.eps, delta=delta, resid_out=resid)
             qkv = ops.linear(a, t[p + "wqkv"], bias=t[p + "bqkv_lm"] if c.qkv_bias else None)
-            if grouping is None and M <= ops.fused_attention_rows() and D == 128:
+            if kv.n_pages:
+                q = ops.rope_kv_write_paged(qkv, pos, slot, self.cs, kv.pk[i], kv.pv[i], kv.page_table, H, Hkv, D, cpos=cpos)
+                att = ops.decode_attention_paged(q, kv.pk[i], kv.pv[i], kv.page_table, attn_rows, H, Hkv, D, kv.kp[i], kv.vp[i],
+                                                 kv.t_pre + kv.own_span, workspace)
+            elif grouping is None and M <= ops.fused_attention_rows() and D == 128:
                 # a few rows (one question in flight): RoPE + KV write + attention + merge in one launch
                 att = ops.decode_attention_fused(qkv, pos, cpos, slot, self.cs, kv.ko[i], kv.vo[i], attn_rows, H, Hkv, D,
                                                  k_prefix=kv.kp[i], v_prefix=kv.vp[i])
@@ -759,7 +785,7 @@ class _DecodeRunner:
         lm = eng.cfg.lm
         # the step's own partials buffer (also for the ungrouped split-KV pass): a captured graph must not point into a
         # shared buffer that a later, larger call re-allocates
-        self.workspace = ops.attention_workspace(R, lm.n_heads, lm.head_dim, kv.t_pre + (kv.t_own + 63) // 64 * 64, dev)
+        self.workspace = ops.attention_workspace(R, lm.n_heads, lm.head_dim, kv.t_pre + (kv.own_span + 63) // 64 * 64, dev)
         if tail.get("n_groups", 0) > 0:
             self.grouping = dict(groups=torch.zeros(max(1, tail["n_groups"]), 4, **i32), group_rows=torch.zeros(R, **i32),
                                  n_groups=tail["n_groups"], items=torch.zeros(max(1, tail["n_items"]), 4, **i32), n_items=tail["n_items"],
@@ -885,6 +911,16 @@ class _DecodeRunner:
         (`slot`), so nothing moves in the pools - the smaller step just lists the surviving rows."""
         rows_idx = self._take(old, q_idx)
         self.slot.copy_(old.slot[rows_idx]); self.gen.copy_(old.gen[q_idx]); self.s0.copy_(old.s0[q_idx])
+
+    def vacate(self, q_idx: torch.Tensor):
+        """Admission mode, paged own KV: the questions in the slots q_idx are taken out of the batch (preempted).  Their rows become the
+        harmless rows of free slots - one own key, position 0 of the idle rows' page - until a waiting question takes the slot."""
+        r_idx = torch.cat([q_idx + b * self.Q for b in range(self.nb)])
+        self.unfinished.index_fill_(0, q_idx, 0)
+        self.pos.index_fill_(0, r_idx, 0); self.cpos.index_fill_(0, r_idx, 0)
+        own = self.rows[r_idx]
+        own[:, 1], own[:, 2], own[:, 3] = 1, 0, 0
+        self.rows.index_copy_(0, r_idx, own)
 
     def failed(self) -> torch.Tensor:                           # device bool: a row lost every finite score
         return (self.status | self.status0).ne(0).any()
@@ -1016,7 +1052,7 @@ class VddLlavaEngine:
         # decode attention reads each shared prompt prefix once per GROUP of rows (K/V tiles staged in LDS)
         self.group_attention = True
         self._kv: Optional[KVCache] = None          # the pools of the most recent call
-        self._kvs: Dict[bool, KVCache] = {}
+        self._kvs: Dict[object, KVCache] = {}           # pool form (frag_only False / True, "paged") -> its cache
         self._feat_cache: Dict[int, torch.Tensor] = {}
         self._prefill_cache: Optional[dict] = None           # generate(reuse_prefill=True): plan, pools and step-0 logits of the last such call
         self._graphs: dict = {}
@@ -1025,38 +1061,42 @@ class VddLlavaEngine:
         self.call_log: Optional[list] = None
 
     # -- plumbing ---------------------------------------------------------------------------
-    def kv(self, n_pre, t_pre, n_own, t_own, frag_only=False):
-        """The KV pools for a call, one cache per prefix-pool form (KVCache.frag_only): a driver alternates calls that group their
-        decode rows (the image questions) with calls that do not (a handful of rows), and each keeps its pools - and the decode
-        graphs captured over them - across calls; a cache only grows."""
+    def kv(self, n_pre, t_pre, n_own, t_own, frag_only=False, n_pages=0, max_pages=0):
+        """The KV pools for a call, one cache per pool form (KVCache.frag_only, or "paged" for the paged own-KV form of generate_list): a
+        driver alternates calls that group their decode rows (the image questions) with calls that do not (a handful of rows), and each
+        keeps its pools - and the decode graphs captured over them - across calls; a cache only grows."""
         # prefix slots are whole 64-key chunks (the fragment image); own slots only need whole 16-key groups: 92 own tokens take
         # 96 rows, not 128 (a quarter of the own pool, 26 GB at 768 questions)
         t_pre, t_own = (max(t_pre, 64) + 63) // 64 * 64, (max(t_own, 64) + 15) // 16 * 16
-        cur = self._kvs.get(frag_only)
-        if cur is None or not cur.fits(n_pre, t_pre, n_own, t_own, frag_only):
-            self._kvs.pop(frag_only, None)
+        form = "paged" if n_pages else frag_only
+        cur = self._kvs.get(form)
+        if cur is None or not cur.fits(n_pre, t_pre, n_own, t_own, frag_only, n_pages, max_pages):
+            self._kvs.pop(form, None)
             self._drop_graphs(cur)
             grow = lambda a, b: max(a, b)
             if cur is not None:
                 n_pre, t_pre, n_own, t_own = grow(n_pre, cur.n_pre), grow(t_pre, cur.t_pre), grow(n_own, cur.n_own), grow(t_own, cur.t_own)
+                n_pages, max_pages = grow(n_pages, cur.n_pages), grow(max_pages, cur.max_pages)
             if self._kv is cur:
                 self._kv = None
             del cur
-            need = KVCache.bytes_needed(self.cfg.lm, n_pre, t_pre, n_own, t_own, self.dtype, frag_only)
-            other = self._kvs.get(not frag_only)
-            if other is not None and self.device.type == "cuda":
+            need = KVCache.bytes_needed(self.cfg.lm, n_pre, t_pre, n_own, t_own, self.dtype, frag_only, n_pages)
+            for other_form in [f for f in self._kvs if f != form]:
+                if self.device.type != "cuda":
+                    break
                 free, _total = torch.cuda.mem_get_info(self.device)
                 if need > free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device):
-                    # both forms do not fit side by side: the other one (and its graphs) goes
+                    # the forms do not fit side by side: another one (and its graphs) goes
+                    other = self._kvs.pop(other_form)
                     self._drop_graphs(other)
-                    self._kvs.pop(not frag_only)
                     if self._kv is other:
                         self._kv = None
                     del other
                     gc.collect()
                     torch.cuda.empty_cache()
-            self._kvs[frag_only] = KVCache(self.cfg.lm, n_pre, t_pre, n_own, t_own, self.device, self.dtype, frag_only=frag_only)
-        self._kv = self._kvs[frag_only]
+            self._kvs[form] = KVCache(self.cfg.lm, n_pre, t_pre, n_own, t_own, self.device, self.dtype, frag_only=frag_only, n_pages=n_pages,
+                                      max_pages=max_pages)
+        self._kv = self._kvs[form]
         return self._kv
 
     # Distinct images per vision-tower forward.  The tower's GEMMs have K = 1,024 / 4,096 and N = 1,024 ... 4,096: at 16 images (9,232
@@ -1457,7 +1497,8 @@ class VddLlavaEngine:
                       embeds_prefix: Optional[Sequence[Optional[tuple]]] = None, cd_alpha: Optional[float] = None, cd_beta: Optional[float] = None, use_dd: bool = False, use_dd_unk: bool = False,
                       temperature: Optional[float] = None, top_p: Optional[float] = None, top_k: Optional[int] = None,
                       max_new_tokens: int = 64, eos_token_id=None, pad_token_id: Optional[int] = None, cd_greedy: bool = False,
-                      n_top: int = 0, seed: Optional[int] = None, sync_every: int = 8, admit_min: Optional[int] = None) -> GenerateOutput:
+                      n_top: int = 0, seed: Optional[int] = None, sync_every: int = 8, admit_min: Optional[int] = None,
+                      paged_kv: bool = False, kv_page_budget: Optional[int] = None) -> GenerateOutput:
         """The reference walks an arbitrarily long question list one generate() call at a time (llava_sampling.py:78-116: LLaVA-Bench, answers
         of 20 - 1,000 tokens; llava_calibrate.py:130).  generate() decodes ONE batch to its end - the last rows of a batch of open-ended
         answers run almost alone.  This call takes the whole list and keeps `in_flight` questions decoding: when questions have emitted EOS
@@ -1473,7 +1514,13 @@ class VddLlavaEngine:
         admit_min: waiting questions are admitted once that many slots are free (default in_flight / 16; prefilling a handful of questions
         costs a pass over the weights like a decode step of the whole batch).  Returns a GenerateOutput over ALL questions, input order;
         stats: admissions, decode steps, mean live rows per step.  In batch-invariant mode with cd_greedy every answer equals the one
-        generate() gives the question in any batch."""
+        generate() gives the question in any batch.
+        paged_kv=True: own-KV memory follows the tokens really generated instead (paged_kv.py: PAGE-token pages behind a page table, handed
+        out poll by poll; the contiguous own pool shrinks to a staging area for the admission prefill).  The pool is the smaller of the
+        worst case and what the device holds, or `kv_page_budget` pages; below the worst case a question can be preempted - taken out,
+        its answer so far discarded, prefilled again later (stats['preemptions']) - so the call cannot deadlock.  Same answers in a
+        deterministic decode; a sampled decode draws a preempted question afresh (still reproducible for a seed: the schedule depends
+        only on the polled finished flags).  in_flight is then only lowered when not even the staging pool + one question fit."""
         dev, lm = self.device, self.cfg.lm
         if eos_token_id is None:
             raise ValueError("generate_list needs eos_token_id: without an EOS every answer has max_new_tokens tokens and generate() in batches does the same work")
@@ -1548,15 +1595,27 @@ class VddLlavaEngine:
         # VCD: every admitted question's cd prompt (tokens | noised patches | suffix) is prefilled as ONE sequence into a scratch prefix slot
         t_pool = max(t_pre, longest) if vcd else t_pre
         pre_slots = lambda q_: (2 if vcd else 1) * q_ + len(shared_keys) + 1
-        Qc = self._fit_in_flight(Qc, lambda q_: (pre_slots(q_), t_pool, nb * q_, suffix_cap + max_new_tokens))
+        if kv_page_budget is not None and not paged_kv:
+            raise ValueError("generate_list: kv_page_budget sizes the page pool of paged_kv=True")
+        if paged_kv:
+            Qc, n_pages = self._fit_paged(Qc, lambda q_: (pre_slots(q_), t_pool, nb * q_, suffix_cap), nb, pages_for(suffix_cap + max_new_tokens),
+                                          kv_page_budget)
+        else:
+            Qc = self._fit_in_flight(Qc, lambda q_: (pre_slots(q_), t_pool, nb * q_, suffix_cap + max_new_tokens))
         admit_min = min(admit_min, max(1, Qc // 2))
         n_pre = pre_slots(Qc)
-        kv = self.kv(n_pre, t_pool, nb * Qc, suffix_cap + max_new_tokens, frag_only=False)
+        if paged_kv:
+            pager = ListPager(n_pages, Qc, nb, suffix_cap, max_new_tokens, sync_every)
+            kv = self.kv(n_pre, t_pool, nb * Qc, suffix_cap, n_pages=n_pages, max_pages=pager.max_pages)
+            pager.alloc.pad_table(kv.n_own, kv.max_pages)        # a cache that grew in an earlier call: the device table has its shape
+        else:
+            pager = None
+            kv = self.kv(n_pre, t_pool, nb * Qc, suffix_cap + max_new_tokens, frag_only=False)
         self._forget_kept_prefill(kv)
         eos_t = h2d_long(dev, eos_token_id)
         ctr0 = self._philox_counter(seed)
         cfgkey = ("list", Qc, nb, max_new_tokens, alpha, beta, warp.t, warp.k, warp.p, use_dd, use_dd_unk, vcd, cd_greedy, tuple(eos_token_id), pad_token_id,
-                  ops.GEMM_BATCH_INVARIANT)
+                  ops.GEMM_BATCH_INVARIANT) + (("paged",) if paged_kv else ())
         tail = dict(alpha=alpha, beta=beta, warp=warp, contrast=contrast, is_vcd=vcd, both=(use_dd and use_dd_unk), greedy=cd_greedy, eos_t=eos_t,
                     pad=pad_token_id, output_scores=False, n_groups=0, n_items=0, cpi=1, proc={}, admit=True)
         run = self._runner(cfgkey, Qc, nb, max_new_tokens, tail, kv)
@@ -1567,25 +1626,37 @@ class VddLlavaEngine:
         run.pos.zero_(); run.cpos.zero_(); run.s0.zero_(); run.gen.fill_(pad_token_id)
         run.rows.copy_(torch.tensor([[r_, 1, 0, 0] for r_ in range(nb * Qc)], dtype=torch.int32).to(dev))
         for i in range(lm.n_layers):
-            kv.ko[i][:, :, :1].zero_(); kv.vo[i][:, :, :1].zero_()
+            if paged_kv:                                         # ... of page 0, the first page of every slot that holds no question
+                kv.pk[i][:1, :, :1].zero_(); kv.pv[i][:1, :, :1].zero_()
+            else:
+                kv.ko[i][:, :, :1].zero_(); kv.vo[i][:, :, :1].zero_()
         master = torch.full((N, max_new_tokens), pad_token_id, dtype=torch.long, device=dev)
         top_prob = torch.zeros(N, n_top, dtype=torch.float32, device=dev) if n_top else None
         top_tok = torch.zeros(N, n_top, dtype=torch.long, device=dev) if n_top else None
         free_pre = list(range(n_pre - 1, -1, -1))
         table: Dict[tuple, dict] = {}                            # prefix key -> {slot, ref, T, feat (kept alive: its address is part of nobody's key)}
         slot_q = [-1] * Qc                                       # question in each slot
+        slot_own = list(range(Qc))                               # own-slot id of branch 0 of each slot of the running step (the tail shrink drops slots)
+        suffix_len = [int(e.shape[0]) - p_[1] for e, p_ in zip(emb_all, emb_pre)] if emb_mode else [len(r) - si - 1 for r, si in zip(ids_all, s_img)]
         slot_keys: List[list] = [[] for _ in range(Qc)]
         feat_of: Dict[int, torch.Tensor] = {}
         waiting = list(range(N))
         stats = {"n_rows": nb * Qc, "questions": N, "in_flight": Qc, "in_flight_asked": asked, "admissions": 0, "prefill_tokens": 0, "steps": 0, "graph": False}
         live_row_steps = 0
 
-        def retire(slots):
-            """finished slots: their tokens go to `master`, their prefixes lose a reference"""
+        def sync_page_table():
+            """the host's page table -> the static device tensor the captured step reads: one small copy on the stream"""
+            if pager.alloc.dirty:
+                kv.page_table.copy_(h2d_int32(dev, pager.alloc.table)[0])
+                pager.alloc.dirty = False
+
+        def release(slots, keep_tokens):
+            """slots leave the batch: finished (their tokens go to `master`) or preempted; their prefixes lose a reference"""
             if not slots:
                 return
-            idx = torch.tensor(slots, dtype=torch.long, device=dev)
-            master.index_copy_(0, torch.tensor([slot_q[q] for q in slots], dtype=torch.long, device=dev), run.gen[idx, :max_new_tokens])
+            if keep_tokens:
+                idx = torch.tensor(slots, dtype=torch.long, device=dev)
+                master.index_copy_(0, torch.tensor([slot_q[q] for q in slots], dtype=torch.long, device=dev), run.gen[idx, :max_new_tokens])
             for q in slots:
                 for key in slot_keys[q]:
                     e = table[key]
@@ -1597,6 +1668,10 @@ class VddLlavaEngine:
                 slot_q[q], slot_keys[q] = -1, []
                 if im is not None and not any(k_[0] == "img" and k_[2] == im for k_ in table):
                     feat_of.pop(im, None)
+                if paged_kv:
+                    pager.retire(slot_own[q])
+
+        retire = lambda slots: release(slots, True)
 
         def admit(slots):
             """the next len(slots) waiting questions: vision tower for images not seen yet, prefill of new prefixes + all suffixes, first token"""
@@ -1620,7 +1695,7 @@ class VddLlavaEngine:
                         else:
                             key, P, pre = (nm, tuple(r[:si])), len(toks), dict(tokens=toks, img=None)
                         own = dict(tokens=suf, img=None, T=len(suf))
-                    pslot, row = 0, b * Qc + q
+                    pslot, row = 0, b * Qc + slot_own[q]
                     if key is not None:
                         e = table.get(key)
                         if e is None:
@@ -1633,6 +1708,8 @@ class VddLlavaEngine:
                     dec.append((P + own["T"], own["T"], [row, P + own["T"] + 1, pslot, P]))
             for q, i in zip(slots, qs):
                 slot_q[q] = i
+                if paged_kv:
+                    pager.admit(steps, slot_own[q], suffix_len[i])
             passes = [self._prefill_pass(new_pre, to_prefix_pool=True)] if new_pre else []
             scratch = []
             if vcd:
@@ -1647,6 +1724,11 @@ class VddLlavaEngine:
                 passes.append(self._prefill_pass(cd_seq, to_prefix_pool=True, last=True))
             passes.append(self._prefill_pass(suffix, to_prefix_pool=False, last=True, packs=True))
             outs = self.lm.prefill(passes, kv)
+            if paged_kv:                        # the suffixes' K / V: staging slots -> the pages the rows were just given
+                sync_page_table()
+                sl_, nt_ = h2d_int32(dev, [s_["slot"] for s_ in suffix], [s_["T"] for s_ in suffix])
+                for i_ in range(lm.n_layers):
+                    ops.kv_pages_scatter(kv.ko[i_], kv.vo[i_], kv.pk[i_], kv.pv[i_], kv.page_table, sl_, nt_, max(s_["T"] for s_ in suffix))
             resid, delta = outs[-1]
             logits0 = self.lm.logits(resid, delta)                                  # [nb * k, V], branch-major
             k = len(slots)
@@ -1685,8 +1767,12 @@ class VddLlavaEngine:
             e1.record(torch.cuda.current_stream(dev))
             ev_pairs.append((e0, e1))
 
-        timed_admit(list(range(Qc)))
         steps, marks = 0, []
+        if paged_kv:
+            sync_page_table()
+            timed_admit(list(range(pager.n_admissible(0, [suffix_len[i] for i in waiting[:Qc]]))))
+        else:
+            timed_admit(list(range(Qc)))
         while True:
             run.step(kv)
             steps += 1
@@ -1699,6 +1785,21 @@ class VddLlavaEngine:
                 break
             Qr = run.Q
             done = [q for q in range(Qr) if not unf_h[q] and slot_q[q] >= 0]
+            preempted = []
+            if paged_kv:
+                # finished questions give their pages back at once; every live row gets the pages the steps up to the next poll can write -
+                # and when the pool cannot cover that, the most recently admitted questions go back to the head of the waiting list
+                retire(done)
+                done = []
+                at_slot = {slot_own[q]: q for q in range(Qr)}
+                preempted = [at_slot[s_] for s_ in pager.provision(steps, [slot_own[q] for q in range(Qr) if unf_h[q]])]    # oldest admission first
+                if preempted:
+                    run.vacate(torch.tensor(preempted, dtype=torch.long, device=dev))
+                    waiting[:0] = [slot_q[q] for q in preempted]
+                    release(preempted, False)
+                    for q in preempted:
+                        unf_h[q] = 0
+                sync_page_table()
             if not waiting:
                 if not any(unf_h):
                     break
@@ -1709,11 +1810,15 @@ class VddLlavaEngine:
                     retire(done)
                     small = self._runner(cfgkey + ("tail", len(live)), len(live), nb, max_new_tokens, tail, kv)
                     small.adopt_slots(run, torch.tensor(live, dtype=torch.long, device=dev))
-                    slot_q, slot_keys = [slot_q[q] for q in live], [slot_keys[q] for q in live]
+                    slot_q, slot_keys, slot_own = [slot_q[q] for q in live], [slot_keys[q] for q in live], [slot_own[q] for q in live]
                     run = small
                     stats["tail_shrinks"] = stats.get("tail_shrinks", 0) + 1
                 continue
             free = [q for q in range(Qr) if not unf_h[q]]
+            if paged_kv:                # as many of the waiting questions as the free pages cover (suffix + one poll interval; ListPager.n_admissible)
+                free = free[:pager.n_admissible(steps, [suffix_len[i] for i in waiting[:len(free)]])]
+                if not free:
+                    continue
             if len(free) >= min(admit_min, len(waiting)) or not any(unf_h):
                 retire(done)
                 timed_admit(free[:len(waiting)])
@@ -1724,7 +1829,10 @@ class VddLlavaEngine:
         gen = gen.clone()
         seqs_out = prompt_plus_answer(dev, ids_all, gen)        # (embedding prompts: ids_all is empty per question - the new tokens alone)
         stats.update(steps=steps, graph=run.graph is not None, answer_tokens=int(done_at.sum().item()) + N,
-                     mean_live_rows=round(live_row_steps / max(steps, 1), 1), n_groups=0)
+                     mean_live_rows=round(live_row_steps / max(steps, 1), 1), n_groups=0, paged_kv=bool(paged_kv),
+                     own_kv_bytes=2 * sum(t_.numel() * t_.element_size() for t_ in ((kv.pk + kv.ko) if paged_kv else kv.ko)))
+        if paged_kv:
+            stats.update(pager.stats())
         return GenerateOutput(seqs_out, gen, None, top_prob, top_tok, stats)
 
     share_repeated_rows = True        # _plan: image-free rows with identical ids share all but their last position
@@ -1753,6 +1861,34 @@ class VddLlavaEngine:
         while Qc > 8 and not fits_current(Qc) and need(Qc) > self.KV_MEMORY_FRACTION * avail:
             Qc = max(8, Qc * 7 // 8)
         return Qc
+
+    def _fit_paged(self, Qc: int, dims, nb: int, max_pages: int, budget: Optional[int]):
+        """generate_list(paged_kv=True) -> (questions in flight, pages of the pool).  The paged form costs prefix pools + staging pool
+        `dims(Qc)` + page pool; the page pool is `budget` pages when given (ListPager refuses one that cannot hold a question at full
+        length), else the smaller of the worst case - every slot at full length - and what KV_MEMORY_FRACTION of the free memory leaves.
+        The number in flight is only lowered (by eighths, not below 8) while not even the smallest useful pool fits next to the rest."""
+        lm = self.cfg.lm
+        worst = lambda q_: nb * q_ * max_pages + 1
+        floor = lambda q_: nb * max_pages + 1                         # one question at full length + the idle rows' shared page
+        if budget is not None:
+            return Qc, int(budget)
+        if self.device.type != "cuda":
+            return Qc, worst(Qc)
+        cur = self._kvs.get("paged")
+        free, _total = torch.cuda.mem_get_info(self.device)
+        avail = free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device) + (cur.nbytes() if cur is not None else 0)
+        page_bytes = KVCache.bytes_needed(lm, 0, 0, 0, 0, self.dtype, False, n_pages=1)
+
+        def room(q_):
+            n_pre, t_pre, n_own, t_own = dims(q_)
+            t_pre, t_own = (max(t_pre, 64) + 63) // 64 * 64, (max(t_own, 64) + 15) // 16 * 16
+            if cur is not None:
+                n_pre, t_pre, n_own, t_own = max(n_pre, cur.n_pre), max(t_pre, cur.t_pre), max(n_own, cur.n_own), max(t_own, cur.t_own)
+            rest = KVCache.bytes_needed(lm, n_pre, t_pre, n_own, t_own, self.dtype, False)
+            return int((self.KV_MEMORY_FRACTION * avail - rest) // page_bytes)
+        while Qc > 8 and room(Qc) < floor(Qc):
+            Qc = max(8, Qc * 7 // 8)
+        return Qc, max(floor(Qc), min(worst(Qc), room(Qc)))
 
     def _processor_config(self, prompt_lens, ids_list, eos_token_id, min_new_tokens, min_length, stop_words_ids, repetition_penalty,
                           logits_processor, max_new_tokens):

@@ -39,6 +39,9 @@ _SIGS = {
     "vdd_skinny_gemm_resid_ss": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _P],
     "vdd_skinny_gemm_normed": [_P, _P, _I, _P, _F, _P, _P, _I, _I, _I, _L, _L, _I, _P],
     "vdd_skinny_swiglu_normed": [_P, _P, _I, _P, _F, _P, _P, _I, _I, _I, _L, _I, _P],
+    "vdd_rope_kv_write_paged": [_P] * 9 + [_I, _I, _I, _I, _L, _I, _I, _I, _I, _P],
+    "vdd_decode_attention_paged": [_P] * 9 + [_I, _I, _I, _I, _L, _I, _I, _I, _L, _I, _I, _F, _I, _P],
+    "vdd_kv_pages_scatter": [_P] * 7 + [_I, _I, _I, _I, _L, _I, _L, _I, _I, _I, _I, _P],
     "vdd_stop_words_match": [_P, _L, _L, _P, _P, _I, _P, _P, _I, _P, _I, _P],
     "vdd_repetition_penalty": [_P, _L, _I, _I, _I, _P, _I, _P, _L, _L, _P, _F, C.c_uint32, _P],
 }
@@ -113,6 +116,39 @@ def rope_kv_write(qkv, pos, slot, cos_sin, k_cache, v_cache, Hq, Hkv, D, q_out=N
                                               k_cache.data_ptr(), v_cache.data_ptr(), M, Hq, Hkv, D, k_cache.stride(0),
                                               k_cache.shape[2], dt, _st(qkv)))
     return q_out
+
+
+def _page_pool(k_pages, v_pages, page_table):
+    """(page_stride, n_pages, n_slots, max_pages_per_slot) of a paged own-KV pool [n_pages, Hkv, KV_PAGE, D] + its int32 table."""
+    from .paged_kv import PAGE
+    if (k_pages.dim() != 4 or k_pages.shape[2] != PAGE or k_pages.shape != v_pages.shape or not k_pages.is_contiguous() or not v_pages.is_contiguous()
+            or page_table.dtype != torch.int32 or page_table.dim() != 2 or not page_table.is_contiguous()):
+        raise ValueError(f"paged own-KV: contiguous pools [n_pages, Hkv, {PAGE}, D] and a contiguous int32 table [n_slots, max_pages_per_slot]")
+    return k_pages.stride(0), k_pages.shape[0], page_table.shape[0], page_table.shape[1]
+
+
+def rope_kv_write_paged(qkv, pos, slot, cos_sin, k_pages, v_pages, page_table, Hq, Hkv, D, q_out=None, cpos=None):
+    """rope_kv_write into a paged own-KV pool: K / V of row m go to page page_table[slot[m]][cpos[m] // PAGE], index cpos[m] % PAGE
+    (no page there: not stored).  Returns rotated q [M, Hq*D], bit-identical to rope_kv_write's."""
+    dt = _dt(qkv, k_pages, v_pages)
+    M = qkv.shape[0]
+    q_out = torch.empty(M, Hq * D, dtype=qkv.dtype, device=qkv.device) if q_out is None else q_out
+    cpos = pos if cpos is None else cpos
+    _lib.check(_lib_ready().vdd_rope_kv_write_paged(qkv.data_ptr(), pos.data_ptr(), cpos.data_ptr(), slot.data_ptr(), cos_sin.data_ptr(), q_out.data_ptr(),
+                                                    k_pages.data_ptr(), v_pages.data_ptr(), page_table.data_ptr(), M, Hq, Hkv, D,
+                                                    *_page_pool(k_pages, v_pages, page_table), dt, _st(qkv)))
+    return q_out
+
+
+def kv_pages_scatter(k_own, v_own, k_pages, v_pages, page_table, slots, n_tok, max_tok):
+    """The first n_tok[r] (<= max_tok) tokens of the contiguous own slots slots[r] (int32 device tensors) -> the pages of those slots;
+    k_own / v_own [n_slots, Hkv, t_max, D] with one slot per table row.  One layer per call."""
+    dt = _dt(k_own, v_own, k_pages, v_pages)
+    if k_own.shape[0] != page_table.shape[0] or k_own.shape != v_own.shape or k_own.stride()[1:] != v_own.stride()[1:] or k_own.stride(0) != v_own.stride(0):
+        raise ValueError("kv_pages_scatter: one contiguous own slot per page-table row, K and V pools of one layout")
+    _lib.check(_lib_ready().vdd_kv_pages_scatter(k_own.data_ptr(), v_own.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), page_table.data_ptr(),
+                                                 slots.data_ptr(), n_tok.data_ptr(), int(slots.numel()), int(max_tok), k_own.shape[1], k_own.shape[3],
+                                                 k_own.stride(0), k_own.shape[2], *_page_pool(k_pages, v_pages, page_table), dt, _st(k_own)))
 
 
 def silu_mul(gate_up, out=None):
@@ -823,6 +859,24 @@ def decode_attention(q, k_cache, v_cache, rows, H, Hkv, D, out=None, max_len=Non
     _lib.check(lib.vdd_decode_attention(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_prefix.data_ptr(), v_prefix.data_ptr(),
                                         rows.data_ptr(), out.data_ptr(), ws.data_ptr(), M, H, Hkv, D, k_cache.stride(0), k_cache.shape[2],
                                         k_prefix.stride(0), k_prefix.shape[2], max_len, D ** -0.5, dt, _st(q)))
+    return out
+
+
+def decode_attention_paged(q, k_pages, v_pages, page_table, rows, H, Hkv, D, k_prefix, v_prefix, max_len, workspace, out=None):
+    """decode_attention with the own range of every row read through the page table (rows[m, 0] = own-slot id = table row); the
+    prefixes come from the row-major pools k_prefix / v_prefix.  Bit-identical to decode_attention over contiguous slots holding
+    the same K / V.  `workspace`: attention_workspace(M, H, D, max_len, device) or larger."""
+    dt = _dt(q, k_pages, v_pages, k_prefix, v_prefix)
+    M = q.shape[0]
+    lib = _lib_ready()
+    lib.vdd_decode_attention_workspace_bytes.restype = C.c_int64
+    if workspace.numel() * 4 < lib.vdd_decode_attention_workspace_bytes(M, H, D, int(max_len)):
+        raise ValueError("attention workspace too small")
+    out = torch.empty_like(q) if out is None else out
+    _lib.check(lib.vdd_decode_attention_paged(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), page_table.data_ptr(), k_prefix.data_ptr(),
+                                              v_prefix.data_ptr(), rows.data_ptr(), out.data_ptr(), workspace.data_ptr(), M, H, Hkv, D,
+                                              *_page_pool(k_pages, v_pages, page_table), k_prefix.stride(0), k_prefix.shape[2], int(max_len),
+                                              D ** -0.5, dt, _st(q)))
     return out
 
 

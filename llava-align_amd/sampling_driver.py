@@ -33,12 +33,14 @@ def run_sampling(engine: VddLlavaEngine, questions: Sequence[dict], encode: Call
                  load_image: Callable[[str], torch.Tensor], answers_path: Optional[str] = None, model_id: str = "llava-align_amd",
                  pope_suffix: bool = False, in_flight: int = 90, max_new_tokens: int = 1024, eos_token_id=2, pad_token_id: Optional[int] = 0,
                  stop_str: Optional[str] = "</s>", noise_step: Optional[int] = None, rank: Optional[int] = None, world: Optional[int] = None,
-                 batch_invariant: Optional[bool] = None, **generate_kw) -> dict:
+                 batch_invariant: Optional[bool] = None, paged_kv: bool = False, **generate_kw) -> dict:
     """questions: dicts with question_id, image, text.  generate_kw: cd_alpha, cd_beta, use_dd, use_dd_unk, temperature, top_p, top_k, seed,
     cd_greedy - the reference's generate kwargs (llava_sampling.py:96-109; temperature 0 there means greedy: pass do_sample=False).
     rank / world (default: the initialised torch.distributed group): every rank decodes its contiguous chunk of whole images
     (shard.ShardPlan), ONE collective gathers the answers, rank 0 writes the file; every rank returns the full result.  Deterministic decodes
     run in batch-invariant mode unless told otherwise (shard.resolve_batch_invariant): same answers on 1 and N ranks, at any in_flight.
+    paged_kv: engine.generate_list(paged_kv=True) - own-KV memory follows the tokens really generated, so `in_flight` questions fit at
+    max_new_tokens=1024 where full-length slots would not.
     Returns {"answers": [...], "stats": the engine's stats of this rank's chunk}."""
     run = ShardedRun(questions, rank, world, generate_kw, batch_invariant)
     mine, generate_kw = run.mine, run.generate_kw
@@ -52,7 +54,8 @@ def run_sampling(engine: VddLlavaEngine, questions: Sequence[dict], encode: Call
             kw = {k: v for k, v in generate_kw.items() if k != "do_sample"}
             if noise_step is not None:
                 kw["images_cd"] = [add_diffusion_noise(im, noise_step) for im in imgs]                 # fresh noise per question (:88-91)
-            out = engine.generate_list(ids, imgs, in_flight=in_flight, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, **kw)
+            out = engine.generate_list(ids, imgs, in_flight=in_flight, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                                       paged_kv=paged_kv, **kw)
             rows.add(mine, out.tokens)
             stats = out.stats
         elif mine:                  # do_sample=False: greedy_search is not patched - plain arg-max decoding, batch after batch
@@ -83,6 +86,7 @@ def _parser():
     ap.add_argument("--use_dd_unk", action="store_true")
     ap.add_argument("--max_new_tokens", type=int, default=1024)
     ap.add_argument("--in-flight", type=int, default=90)
+    ap.add_argument("--paged-kv", action="store_true", default=argparse.SUPPRESS, help="paged own-KV pool: memory follows the tokens really generated (engine.generate_list(paged_kv=True))")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--naive", action="store_true", help="experiments/eval/llava_naive.py:39-98: ONE run at --temperature / --top_p / --top_k (greedy at "
                     "temperature 0), always with the one-word suffix, into --answers-file as given")
@@ -120,8 +124,8 @@ def main(argv=None):
                            lambda name: K.clip_preprocess(proc, os.path.join(a.image_folder, name)), answers_path=path,
                            model_id=os.path.basename(a.model_path.rstrip("/")), pope_suffix=a.naive or "POPE" in a.question_file, in_flight=a.in_flight,
                            max_new_tokens=a.max_new_tokens, eos_token_id=tok.eos_token_id, pad_token_id=tok.pad_token_id or 0,
-                           noise_step=a.noise_step if a.use_cd else None, rank=rank, world=world, use_dd=a.use_dd, use_dd_unk=a.use_dd_unk,
-                           cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, temperature=temp if temp > 0 else 1.0, top_p=top_p, top_k=top_k, seed=a.seed, **greedy)
+                           noise_step=a.noise_step if a.use_cd else None, rank=rank, world=world, paged_kv=getattr(a, "paged_kv", False), use_dd=a.use_dd,
+                           use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, temperature=temp if temp > 0 else 1.0, top_p=top_p, top_k=top_k, seed=a.seed, **greedy)
         if rank == 0:
             print(json.dumps({"run": tag or "naive", "answers_file": path, "n_answers": len(res["answers"]), "stats": {k: v for k, v in res["stats"].items() if not hasattr(v, "__len__") or isinstance(v, str)}}), flush=True)
     finish_distributed(world)
