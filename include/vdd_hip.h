@@ -33,7 +33,7 @@ extern "C" {
 typedef enum vdd_status {
     VDD_OK = 0,
     VDD_ERR_INVALID_ARG = -1,   /* null/negative/misaligned argument, see vdd_last_error() */
-    VDD_ERR_UNSUPPORTED = -2,   /* reserved */
+    VDD_ERR_UNSUPPORTED = -2,   /* a shape this entry does not serve (the normed / 8-bit projections): take the documented other path */
     VDD_ERR_LAUNCH = -3         /* hipLaunchKernel failed */
 } vdd_status;
 
@@ -204,6 +204,26 @@ int vdd_skinny_gemm_normed(const void* H, const float* ss, int nss, const void* 
                            int K, int64_t ldh, int64_t ldy, int dtype, void* hip_stream);
 int vdd_skinny_swiglu_normed(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W_gate_up, void* act,
                              int M, int F, int K, int64_t ldh, int dtype, void* hip_stream);
+
+/* 8-bit weight rows (load_8bit): the three entries above with W held as OCP e4m3 (`e4m3fn`) codes W8 [N, K] bytes plus one fp32 scale
+ * per output row, w_scale [N] ([2F] for the gate/up pair: gate rows, then up rows), every scale a power of two.  A code times its row's
+ * scale is a bf16 / fp16 value, so the pair denotes a 16-bit weight w16 = code * scale exactly, and each entry returns, bit for bit,
+ * what its 16-bit twin returns on w16: the codes are widened in registers to the 16-bit MFMA fragments (exact for every finite code,
+ * subnormals included), the MFMAs and the order of the fp32 sums are the twin's, and the scale is multiplied onto the fp32 sum before
+ * the first rounding of the epilogue.  The NaN codes 0x7F / 0xFF must not occur.
+ * Storage order of a row (K % 64 == 0): element k of row n lives at byte
+ *     n * K + (k / 64) * 64 + ((k % 32) / 8) * 16 + ((k % 64) / 32) * 8 + k % 8
+ * - inside every aligned group of 64 K-elements, the 8 elements a lane group g = (k % 32) / 8 owns in MFMA k-step 2b sit next to its
+ * 8 elements of k-step 2b + 1, so one 16-byte load per lane covers two k-steps, a row stays contiguous and the element -> MFMA slot
+ * map of the 16-bit kernels is kept (ops.w8_pack / ops.w8_unpack).
+ * M <= 16, K % 256 == 0 and, for the normed forms, the limits of their twins; any other shape returns VDD_ERR_UNSUPPORTED and
+ * launches nothing: the caller runs the 16-bit twin on w16. */
+int vdd_skinny_gemm_resid_ss_w8(const void* X, const void* W8, const float* w_scale, const void* R, void* Y, float* ss_out, int M, int N,
+                                int K, int64_t ldx, int64_t ldr, int64_t ldy, int dtype, void* hip_stream);
+int vdd_skinny_gemm_normed_w8(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W8, const float* w_scale,
+                              void* Y, int M, int N, int K, int64_t ldh, int64_t ldy, int dtype, void* hip_stream);
+int vdd_skinny_swiglu_normed_w8(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W8_gate_up,
+                                const float* w_scale, void* act, int M, int F, int K, int64_t ldh, int dtype, void* hip_stream);
 
 /* Row-batched projection GEMM, any M above the skinny regime (csrc/vdd_gemm.hip): Y[M,N] = epilogue(X[M,K] W[N,K]^T), bf16 in,
  * fp32 accumulate (32x32x16 MFMA, both operands LDS-DMA'd into swizzled LDS tiles, persistent stream-K over one workgroup

@@ -26,7 +26,7 @@ import torch
 from . import calibrate as C
 from . import shard
 from .blip_frontend import InstructBlipFrontEnd
-from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, add_script_args, answer_text, chunk_of, distinct, eos_set, finish_distributed, load_distinct_images,
+from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, load_kw, add_script_args, answer_text, chunk_of, distinct, eos_set, finish_distributed, load_distinct_images,
                             pope_scores_for, read_questions, to_all_rows, write_jsonl)
 from .engine import VddLlavaEngine
 from .vcd_add_noise import add_diffusion_noise
@@ -150,7 +150,7 @@ def main(argv=None):
     front = InstructBlipFrontEnd(BlipWeights.from_state_dict(bcfg, sd, device, dtype=dtype))
     cfg = K.config_from_dir(a.llm_path, fallback="llava-1.5-7b")           # the LM side only: the preset's CLIP tower is unused on this path
     llm_sd = K.load_state_dict(a.llm_path)
-    eng = VddLlavaEngine(cfg, weights=LlavaWeights.lm_from_state_dict(cfg, llm_sd, device, dtype=dtype), device=device)
+    eng = VddLlavaEngine(cfg, weights=LlavaWeights.lm_from_state_dict(cfg, llm_sd, device, dtype=dtype), device=device, **load_kw(a))
     llm_tok = K.load_tokenizer(a.llm_path)
     from transformers import AutoTokenizer
     bert = AutoTokenizer.from_pretrained(a.bert_tokenizer)

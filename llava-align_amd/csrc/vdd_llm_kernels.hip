@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "vdd_elem.h"
+#include "vdd_w8.h"
 
 namespace {
 namespace VDD_ELEM_NS {
@@ -345,6 +346,56 @@ __global__ void __launch_bounds__(256) embed_scatter_kernel(const int* __restric
 //          bf16(bf16(h * rstd) * ln_w[k]) - the roundings of rmsnorm_kernel.
 struct NormIn { const float* ss; int nss; const uint16_t* lnw; float eps; };
 
+// What a lane streams of its weight row, behind one interface for the 16-bit and the 8-bit (e4m3 codes + a power-of-two scale per
+// row, vdd_w8.h) forms of the few-row projections: `ld` fetches a register stage of U 32-deep k-steps at element kk of the wave's K
+// slice, `ld1` the single k-step at element k (the slice's ragged last stage), `frag` turns one k-step of a stage into the MFMA B
+// operand.  Both views feed the SAME fragments (up to the row's scale) to the same MFMAs in the same order; a SCALED view's kernel
+// multiplies `wscale[row]` onto the fp32 sum before the epilogue's first rounding.
+struct Rows16 {                        // [N][K] elements of the storage type
+    typedef uint16_t code_t;
+    typedef frag8_t stage_t;           // one k-step of a lane: W[n][k + 8 g .. + 7], 16 bytes
+    static constexpr bool SCALED = false;
+    const uint16_t* p;
+    __device__ __forceinline__ Rows16(const uint16_t* W, size_t row, int K, int kbeg, int g) : p(W + row * K + kbeg + g * 8) {}
+    template <class I, int U> __device__ __forceinline__ void ld(stage_t (&b)[U], int kk) const {
+#pragma unroll
+        for (int u = 0; u < U; ++u) b[u] = ld_w(p + (I)(kk + 32 * u));
+    }
+    template <class I> __device__ __forceinline__ stage_t ld1(int k) const { return ld_w(p + (I)k); }
+    static __device__ __forceinline__ stage_t zero() { return stage_t{0, 0, 0, 0, 0, 0, 0, 0}; }
+    static __device__ __forceinline__ frag8_t frag(stage_t s) { return s; }
+};
+struct RowsW8 {                        // [N][K] e4m3 codes in the storage order of include/vdd_hip.h ("8-bit weight rows"): the group
+    typedef uint8_t code_t;            // of 64 elements that holds k-steps 2b and 2b + 1 is four 16-byte pieces, one per lane group g:
+    typedef uint2 stage_t;             // its 8 codes of k-step 2b, then its 8 of k-step 2b + 1 - one k-step of a lane is 8 bytes
+    static constexpr bool SCALED = true;
+    const uint8_t* p;                  // the lane's piece of the group that holds the slice's first k-step
+    int odd;                           // ... which is the group's second k-step (a K slice of an odd number of k-steps: K / 256 odd, 8 waves)
+    __device__ __forceinline__ RowsW8(const uint8_t* W, size_t row, int K, int kbeg, int g)
+        : p(W + row * K + (kbeg & ~63) + g * 16), odd(__builtin_amdgcn_readfirstlane((kbeg >> 5) & 1)) {}
+    // a full stage (kk % 64 == 0): U / 2 loads of 16 bytes; from an odd start the two k-steps at the ends are 8-byte loads.  Every code
+    // is read once either way
+    template <class I, int U> __device__ __forceinline__ void ld(stage_t (&b)[U], int kk) const {
+        static_assert(U % 2 == 0, "a 16-byte load is two k-steps");
+        const uint8_t* q = p + (I)kk;
+        if (!odd) {
+#pragma unroll
+            for (int j = 0; j < U / 2; ++j) { const uint4 v = *reinterpret_cast<const uint4*>(q + 64 * j); b[2 * j] = make_uint2(v.x, v.y); b[2 * j + 1] = make_uint2(v.z, v.w); }
+        } else {
+            b[0] = *reinterpret_cast<const uint2*>(q + 8);
+#pragma unroll
+            for (int j = 1; j < U / 2; ++j) { const uint4 v = *reinterpret_cast<const uint4*>(q + 64 * j); b[2 * j - 1] = make_uint2(v.x, v.y); b[2 * j] = make_uint2(v.z, v.w); }
+            b[U - 1] = *reinterpret_cast<const uint2*>(q + 64 * (U / 2));
+        }
+    }
+    template <class I> __device__ __forceinline__ stage_t ld1(int k) const {
+        const int t = (k >> 5) + odd;                                                   // k-step counted from the first group
+        return *reinterpret_cast<const uint2*>(p + (I)((t >> 1) * 64 + (t & 1) * 8));
+    }
+    static __device__ __forceinline__ stage_t zero() { return make_uint2(0u, 0u); }     // code 0x00 = +0
+    static __device__ __forceinline__ frag8_t frag(stage_t s) { return __builtin_bit_cast(frag8_t, w8_widen(s)); }
+};
+
 typedef __attribute__((ext_vector_type(2))) float f32x2_hw;
 // two elements (packed in a dword) -> rnd(rnd(h * rstd) * g) with the hardware's RNE pack conversion (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32)
 __device__ __forceinline__ uint32_t norm_pair(uint32_t hv, uint32_t gv, float rstd) {
@@ -379,10 +430,10 @@ __device__ __forceinline__ float row_rstd(const NormIn& ni, int r, int K) {
 // 16-lane groups ({0-3, 12-15, 20-27}, ...: 16 DISTINCT rows at two adjacent chunks) and the XOR puts those on 16 distinct slots of the
 // 256-byte bank row (a padded stride of 2 K + 64 left them 2-way conflicted: 16 rows cost 33 us where 2 rows - broadcast - cost 21).
 // SWIGLU: a column block is 8 features (gate rows | up rows of W = [Wg; Wu]) with the SiLU * mul epilogue of skinny_swiglu_kernel.
-template <int NW, bool SWIGLU, int RMAX>          // RMAX: M rounded up to 2 / 4 / 8 / 16 (the prologue is straight-line code over RMAX rows)
-__global__ void __launch_bounds__(NW * 64) skinny_normed_kernel(const uint16_t* __restrict__ Hs, const uint16_t* __restrict__ W,
+template <int NW, bool SWIGLU, int RMAX, class WV = Rows16>   // RMAX: M rounded up to 2 / 4 / 8 / 16 (the prologue is straight-line code over RMAX rows)
+__global__ void __launch_bounds__(NW * 64) skinny_normed_kernel(const uint16_t* __restrict__ Hs, const typename WV::code_t* __restrict__ W,
                                                                uint16_t* __restrict__ Y, int M, int N, int K, long long ldh,
-                                                               long long ldy, NormIn ni, int n_cb) {
+                                                               long long ldy, NormIn ni, int n_cb, const float* __restrict__ wscale) {
     extern __shared__ __attribute__((aligned(16))) unsigned char xs[];           // [M][2 K] bytes, chunk-swizzled
     __shared__ float part2[2][NW][64][4];                                         // double-buffered: ONE barrier per column block
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -394,24 +445,24 @@ __global__ void __launch_bounds__(NW * 64) skinny_normed_kernel(const uint16_t* 
     // from clamped addresses and multiplies the k-steps beyond the slice by a zero W fragment
     const int nb = (kq + 32 * U - 1) / (32 * U);
     const bool ragged = (kq % (32 * U)) != 0;
+    typedef typename WV::stage_t wstage_t;
     auto wptr = [&](int cb) {
-        if constexpr (SWIGLU) { int f = cb * 8 + (ln & 7); if (f >= N) f = N - 1; return W + ((size_t)(ln < 8 ? 0 : N) + f) * K + kbeg + g * 8; }
-        else { int nrow = cb * 16 + ln; if (nrow >= N) nrow = N - 1; return W + (size_t)nrow * K + kbeg + g * 8; }
+        if constexpr (SWIGLU) { int f = cb * 8 + (ln & 7); if (f >= N) f = N - 1; return WV(W, (size_t)(ln < 8 ? 0 : N) + f, K, kbeg, g); }
+        else { int nrow = cb * 16 + ln; if (nrow >= N) nrow = N - 1; return WV(W, (size_t)nrow, K, kbeg, g); }
     };
-    frag8_t b0[U], b1[U];
-    auto ldw = [&](frag8_t (&b)[U], const uint16_t* wp, int i) {
+    wstage_t b0[U], b1[U];
+    auto ldw = [&](wstage_t (&b)[U], const WV& wp, int i) {
         const int kk = i * 32 * U;
         if (ragged && i == nb - 1) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) b[u] = ld_w(wp + (kk + 32 * u < kq ? kk + 32 * u : kk));
+            for (int u = 0; u < U; ++u) b[u] = wp.template ld1<int>(kk + 32 * u < kq ? kk + 32 * u : kk);
         } else {
-#pragma unroll
-            for (int u = 0; u < U; ++u) b[u] = ld_w(wp + kk + 32 * u);
+            wp.template ld<int>(b, kk);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
     int cb = blockIdx.x;
-    const uint16_t* wp = wptr(cb < n_cb ? cb : 0);
+    WV wp = wptr(cb < n_cb ? cb : 0);
     if (nb > 0) ldw(b0, wp, 0);                                                // the weight stream starts before anything else:
     bool b1_ahead = false;                                                     // BOTH register stages of the first column block are
     if (nb > 1) { ldw(b1, wp, 1); b1_ahead = true; }                           // in flight under the normalisation prologue
@@ -483,19 +534,19 @@ __global__ void __launch_bounds__(NW * 64) skinny_normed_kernel(const uint16_t* 
     const unsigned char* xrow = xs + (size_t)rr * rstride;
     const int xk0 = (kbeg + g * 8) * 2, xsw = (rr & 15) << 4;
     auto xfrag = [&](int k) { return *reinterpret_cast<const frag8_t*>(xrow + ((xk0 + k * 2) ^ xsw)); };
-    auto mm = [&](const frag8_t (&b)[U], int i, f32x4_t& acc) {
+    auto mm = [&](const wstage_t (&b)[U], int i, f32x4_t& acc) {
         const int kk = i * 32 * U;
         if (ragged && i == nb - 1) {
             const frag8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const bool in = kk + 32 * u < kq;
-                acc = mfma16(xfrag(in ? kk + 32 * u : kk), in ? b[u] : zero, acc);
+                acc = mfma16(xfrag(in ? kk + 32 * u : kk), in ? WV::frag(b[u]) : zero, acc);
             }
         } else {
 #pragma unroll
             for (int u = 0; u < U; ++u)
-                acc = mfma16(xfrag(kk + 32 * u), b[u], acc);
+                acc = mfma16(xfrag(kk + 32 * u), WV::frag(b[u]), acc);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -512,13 +563,19 @@ __global__ void __launch_bounds__(NW * 64) skinny_normed_kernel(const uint16_t* 
         }
         if (it < nb) mm(b0, it, acc);
         const int cb_next = cb + gridDim.x;
-        const uint16_t* wp_next = wptr(cb_next < n_cb ? cb_next : cb);
+        const WV wp_next = wptr(cb_next < n_cb ? cb_next : cb);
         // BOTH register stages of the next column block go out before the barrier: the weight stream does not drain while the block
         // meets.  The partial sums alternate between two LDS buffers: the waves that do not finish the tile go straight on to the
         // next one (a buffer is rewritten two column blocks later, behind the barrier in between).
         if (cb_next < n_cb && nb > 0) { ldw(b0, wp_next, 0); if (nb > 1) { ldw(b1, wp_next, 1); b1_ahead = true; } }
         float (*part)[64][4] = part2[pbuf];
         pbuf ^= 1;
+        // 8-bit weights: the power-of-two scale of the finishing thread's output row(s), fetched ahead of the barrier
+        float sc0 = 1.f, sc1 = 1.f;
+        if constexpr (WV::SCALED) {
+            if constexpr (SWIGLU) { int f = cb * 8 + (tid & 7); if (f >= N) f = N - 1; sc0 = wscale[f]; sc1 = wscale[N + f]; }
+            else { int col = cb * 16 + ln; if (col >= N) col = N - 1; sc0 = wscale[col]; }
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) part[wave][lane][r] = acc[r];
         __syncthreads();
@@ -532,6 +589,7 @@ __global__ void __launch_bounds__(NW * 64) skinny_normed_kernel(const uint16_t* 
                     us = (part[0][lu][q] + part[1][lu][q]) + (part[2][lu][q] + part[3][lu][q]);
                     if constexpr (NW == 8) { gs += (part[4][lg][q] + part[5][lg][q]) + (part[6][lg][q] + part[7][lg][q]);
                                              us += (part[4][lu][q] + part[5][lu][q]) + (part[6][lu][q] + part[7][lu][q]); }
+                    if constexpr (WV::SCALED) { gs *= sc0; us *= sc1; }
                     const float gb = e2f(f2e(gs)), ub = e2f(f2e(us));
                     const float sl = e2f(f2e(gb / (1.f + __expf(-gb))));
                     Y[(size_t)row * ldy + cb * 8 + c] = (uint16_t)f2e(sl * ub);
@@ -544,6 +602,7 @@ __global__ void __launch_bounds__(NW * 64) skinny_normed_kernel(const uint16_t* 
                     const int row = g * 4 + r, col = cb * 16 + ln;
                     float sacc = (part[0][lane][r] + part[1][lane][r]) + (part[2][lane][r] + part[3][lane][r]);
                     if constexpr (NW == 8) sacc += (part[4][lane][r] + part[5][lane][r]) + (part[6][lane][r] + part[7][lane][r]);
+                    if constexpr (WV::SCALED) sacc *= sc0;
                     if (row < M && col < N) Y[(size_t)row * ldy + col] = (uint16_t)f2e(sacc);
                 }
             }
@@ -552,11 +611,12 @@ __global__ void __launch_bounds__(NW * 64) skinny_normed_kernel(const uint16_t* 
     }
 }
 
-template <int MT, int NW, bool NORM = false, bool SSOUT = false>
-__global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W,
+template <int MT, int NW, bool NORM = false, bool SSOUT = false, class WV = Rows16>
+__global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(const uint16_t* __restrict__ X, const typename WV::code_t* __restrict__ W,
                                                              const uint16_t* __restrict__ R, uint16_t* __restrict__ Y,
                                                              float* __restrict__ Yslab, int M, int N, int K, long long ldx,
-                                                             long long ldr, long long ldy, NormIn ni, float* __restrict__ ss_out) {
+                                                             long long ldr, long long ldy, NormIn ni, float* __restrict__ ss_out,
+                                                             const float* __restrict__ wscale) {
     static_assert(!NORM || MT == 1, "normalise-on-load is the <= 16-row path");
     __shared__ float part[NW][MT][64][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -566,8 +626,8 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(const uint16_t* __
     const int kq = K / (NW * (int)gridDim.y);
     const int kbeg = ((int)blockIdx.y * NW + wave) * kq;
     int nrow = n0 + ln; if (nrow >= N) nrow = N - 1;
-    const uint16_t* wp = W + (size_t)nrow * K + kbeg + g * 8;
-    constexpr int WS = 1;
+    const WV wp(W, (size_t)nrow, K, kbeg, g);
+    typedef typename WV::stage_t wstage_t;
     const uint16_t* xp[MT];
 #pragma unroll
     for (int t = 0; t < MT; ++t) { int r = t * 16 + ln; if (r >= M) r = M - 1; xp[t] = X + (size_t)r * ldx + kbeg + g * 8; }
@@ -579,14 +639,14 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(const uint16_t* __
     // one-question step is a chain of these launches: see DESIGN.md section 5).  Same MFMAs in the same order.
     constexpr int U = MT > 2 ? 4 : 8;                  // k-steps per register stage (33 - 64 rows: 4, so that TWO stages of 16 - 20 fragments fit)
     const int nit = kq / (32 * U);
-    frag8_t b0[U], a0[U][MT], b1[U], a1[U][MT];
+    wstage_t b0[U], b1[U];
+    frag8_t a0[U][MT], a1[U][MT];
     constexpr int UG = NORM ? U : 1;
     frag8_t g0[UG], g1[UG];                             // NORM: the ln weights of a batch's k positions
     const uint16_t* gp = NORM ? ni.lnw + kbeg + g * 8 : nullptr;
     float rstd = 1.f;
-    auto ld = [&](frag8_t (&b)[U], frag8_t (&a)[U][MT], frag8_t (&gw)[UG], int kk) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) b[u] = ld_w(wp + (size_t)(kk + 32 * u) * WS);
+    auto ld = [&](wstage_t (&b)[U], frag8_t (&a)[U][MT], frag8_t (&gw)[UG], int kk) {
+        wp.template ld<size_t>(b, kk);
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -597,14 +657,14 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(const uint16_t* __
         }
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto mm = [&](const frag8_t (&b)[U], const frag8_t (&a)[U][MT], const frag8_t (&gw)[UG]) {
+    auto mm = [&](const wstage_t (&b)[U], const frag8_t (&a)[U][MT], const frag8_t (&gw)[UG]) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
                 frag8_t av = a[u][t];
                 if constexpr (NORM) av = __builtin_bit_cast(frag8_t, norm_chunk(__builtin_bit_cast(uint4, av), __builtin_bit_cast(uint4, gw[u]), rstd));
-                acc[t] = mfma16(av, b[u], acc[t]);
+                acc[t] = mfma16(av, WV::frag(b[u]), acc[t]);
             }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -633,11 +693,11 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(const uint16_t* __
     // load -> MFMA is a chain of memory round trips at the end of every block
     const int krem = nit * 32 * U;
     if (krem < kq) {
-        const frag8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+        const wstage_t zero = WV::zero();
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int kk = krem + 32 * u, kc = kk < kq ? kk : krem;
-            b0[u] = ld_w(wp + (size_t)kc * WS);
+            b0[u] = wp.template ld1<size_t>(kc);
 #pragma unroll
             for (int t = 0; t < MT; ++t) a0[u][t] = *reinterpret_cast<const frag8_t*>(xp[t] + kc);
             if constexpr (NORM) g0[u] = *reinterpret_cast<const frag8_t*>(gp + kc);
@@ -651,6 +711,8 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(const uint16_t* __
     for (int t = 0; t < MT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) part[wave][t][lane][r] = acc[t][r];
+    float sc = 1.f;                                     // 8-bit weights: the power-of-two scale of this lane's output column
+    if constexpr (WV::SCALED) sc = wscale[nrow];
     __syncthreads();
     // C/D map of 16x16x32: col = lane & 15, row = (lane >> 4) * 4 + r.  Wave w finishes tile(s) t = w, w+4, ...
     for (int t = wave; t < MT; t += NW) {
@@ -659,6 +721,7 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(const uint16_t* __
             const int row = t * 16 + g * 4 + r, col = n0 + ln;
             float s = (part[0][t][lane][r] + part[1][t][lane][r]) + (part[2][t][lane][r] + part[3][t][lane][r]);
             if constexpr (NW == 8) s += (part[4][t][lane][r] + part[5][t][lane][r]) + (part[6][t][lane][r] + part[7][t][lane][r]);
+            if constexpr (WV::SCALED) s *= sc;
             float sq = 0.f;
             if (row < M && col < N) {
                 if (Yslab != nullptr) { Yslab[((size_t)blockIdx.y * M + row) * N + col] = s; continue; }
@@ -1474,9 +1537,9 @@ static NormedPlan normed_plan(int n_cb, size_t lds_bytes) {
     const int g = (two ? 2 : 1) * n;
     return NormedPlan{n_cb < g ? n_cb : g, !two};
 }
-template <bool SWIGLU>
-static int normed_launch(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W, void* Y, int M, int N, int K,
-                         int64_t ldh, int64_t ldy, int n_cb, void* stream) {
+template <bool SWIGLU, class WV = Rows16>
+static int normed_launch(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W, const float* wscale, void* Y, int M,
+                         int N, int K, int64_t ldh, int64_t ldy, int n_cb, void* stream) {
     const size_t lds = (size_t)M * 2 * (size_t)K;
     if (lds > NORMED_LDS_CAP || K > 8192 || nss > 512) return VDD_ERR_UNSUPPORTED;
     const NormIn ni{ss, nss, (const uint16_t*)ln_w, eps};
@@ -1484,10 +1547,11 @@ static int normed_launch(const void* H, const float* ss, int nss, const void* ln
 #define VDD_NORMED(NW, R)                                                                                                              \
     do {                                                                                                                               \
         static bool attr = false;                                                                                                      \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)skinny_normed_kernel<NW, SWIGLU, R>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+        if (!attr) { (void)hipFuncSetAttribute((const void*)skinny_normed_kernel<NW, SWIGLU, R, WV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                                (int)NORMED_LDS_CAP); attr = true; }                                                    \
-        hipLaunchKernelGGL((skinny_normed_kernel<NW, SWIGLU, R>), dim3(pl.grid), dim3(NW * 64), lds, (hipStream_t)stream,              \
-                           (const uint16_t*)H, (const uint16_t*)W, (uint16_t*)Y, M, N, K, (long long)ldh, (long long)ldy, ni, n_cb);   \
+        hipLaunchKernelGGL((skinny_normed_kernel<NW, SWIGLU, R, WV>), dim3(pl.grid), dim3(NW * 64), lds, (hipStream_t)stream,          \
+                           (const uint16_t*)H, (const typename WV::code_t*)W, (uint16_t*)Y, M, N, K, (long long)ldh, (long long)ldy, ni, \
+                           n_cb, wscale);                                                                                              \
     } while (0)
     if (pl.wide) { if (M <= 8) VDD_NORMED(8, 8); else VDD_NORMED(8, 16); }
     else if (M <= 2) VDD_NORMED(4, 2);
@@ -1610,7 +1674,7 @@ static int skinny_gemm_launch(const void* X, const void* W, const void* R, void*
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((N + 15) / 16, n_split);
     auto x = (const uint16_t*)X; auto w = (const uint16_t*)W; auto r = (const uint16_t*)R; auto y = (uint16_t*)Y;
-#define VDD_SKINNY(MT, NW) hipLaunchKernelGGL((skinny_gemm_kernel<MT, NW>), grid, dim3(NW * 64), 0, st, x, w, r, y, Y_slabs, M, N, K, (long long)ldx, (long long)ldr, (long long)ldy, NormIn{}, (float*)nullptr)
+#define VDD_SKINNY(MT, NW) hipLaunchKernelGGL((skinny_gemm_kernel<MT, NW>), grid, dim3(NW * 64), 0, st, x, w, r, y, Y_slabs, M, N, K, (long long)ldx, (long long)ldr, (long long)ldy, NormIn{}, (float*)nullptr, (const float*)nullptr)
     // few column blocks (N = d projections): eight waves per block split K eight ways instead of fp32 slabs across blocks
     if (M > 16 && n_split == 1 && Y != nullptr && K % 256 == 0 && N > 8192) {          // 17 - 64 rows, wide outputs: 32 columns per block
         const int mt = (M + 15) / 16;
@@ -1663,18 +1727,26 @@ static int skinny_swiglu_launch(const void* X, const void* W, void* act, int M, 
 }
 
 // ---- small-M decoder-layer fusions of the RMSNorm launches (see skinny_gemm_kernel)
+extern "C++" template <class WV>
+static void resid_ss_launch(const void* X, const void* W, const float* wscale, const void* R, void* Y, float* ss_out, int M, int N, int K, int64_t ldx,
+                            int64_t ldr, int64_t ldy, void* stream) {
+    dim3 grid((N + 15) / 16, 1);
+    hipStream_t st = (hipStream_t)stream;
+    if (N <= 8192 && K % 256 == 0 && eight_wave_blocks(N))
+        hipLaunchKernelGGL((skinny_gemm_kernel<1, 8, false, true, WV>), grid, dim3(512), 0, st, (const uint16_t*)X, (const typename WV::code_t*)W,
+                           (const uint16_t*)R, (uint16_t*)Y, (float*)nullptr, M, N, K, (long long)ldx, (long long)ldr, (long long)ldy, NormIn{}, ss_out,
+                           wscale);
+    else
+        hipLaunchKernelGGL((skinny_gemm_kernel<1, 4, false, true, WV>), grid, dim3(256), 0, st, (const uint16_t*)X, (const typename WV::code_t*)W,
+                           (const uint16_t*)R, (uint16_t*)Y, (float*)nullptr, M, N, K, (long long)ldx, (long long)ldr, (long long)ldy, NormIn{}, ss_out,
+                           wscale);
+}
+
 VDD_HIDDEN int VDD_IMPL(vdd_skinny_gemm_resid_ss)(const void* X, const void* W, const void* R, void* Y, float* ss_out, int M, int N, int K, int64_t ldx,
                              int64_t ldr, int64_t ldy, void* stream) {
     if (M <= 0 || N <= 0) return VDD_OK;
     if (!X || !W || !R || !Y || !ss_out || M > 16 || K % 128 != 0 || (ldx % 8) != 0) return VDD_ERR_INVALID_ARG;
-    dim3 grid((N + 15) / 16, 1);
-    hipStream_t st = (hipStream_t)stream;
-    if (N <= 8192 && K % 256 == 0 && eight_wave_blocks(N))
-        hipLaunchKernelGGL((skinny_gemm_kernel<1, 8, false, true>), grid, dim3(512), 0, st, (const uint16_t*)X, (const uint16_t*)W, (const uint16_t*)R,
-                           (uint16_t*)Y, (float*)nullptr, M, N, K, (long long)ldx, (long long)ldr, (long long)ldy, NormIn{}, ss_out);
-    else
-        hipLaunchKernelGGL((skinny_gemm_kernel<1, 4, false, true>), grid, dim3(256), 0, st, (const uint16_t*)X, (const uint16_t*)W, (const uint16_t*)R,
-                           (uint16_t*)Y, (float*)nullptr, M, N, K, (long long)ldx, (long long)ldr, (long long)ldy, NormIn{}, ss_out);
+    resid_ss_launch<Rows16>(X, W, nullptr, R, Y, ss_out, M, N, K, ldx, ldr, ldy, stream);
     return ok(hipSuccess);
 }
 
@@ -1682,14 +1754,41 @@ VDD_HIDDEN int VDD_IMPL(vdd_skinny_gemm_normed)(const void* H, const float* ss, 
                            int K, int64_t ldh, int64_t ldy, void* stream) {
     if (M <= 0 || N <= 0) return VDD_OK;
     if (!H || !ss || nss <= 0 || (nss % 4) != 0 || !ln_w || !W || !Y || M > 16 || K % 256 != 0 || (ldh % 8) != 0) return VDD_ERR_INVALID_ARG;
-    return normed_launch<false>(H, ss, nss, ln_w, eps, W, Y, M, N, K, ldh, ldy, (N + 15) / 16, stream);
+    return normed_launch<false>(H, ss, nss, ln_w, eps, W, nullptr, Y, M, N, K, ldh, ldy, (N + 15) / 16, stream);
 }
 
 VDD_HIDDEN int VDD_IMPL(vdd_skinny_swiglu_normed)(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W_gate_up, void* act,
                              int M, int F, int K, int64_t ldh, void* stream) {
     if (M <= 0 || F <= 0) return VDD_OK;
     if (!H || !ss || nss <= 0 || (nss % 4) != 0 || !ln_w || !W_gate_up || !act || M > 16 || K % 256 != 0 || (ldh % 8) != 0) return VDD_ERR_INVALID_ARG;
-    return normed_launch<true>(H, ss, nss, ln_w, eps, W_gate_up, act, M, F, K, ldh, (int64_t)F, (F + 7) / 8, stream);
+    return normed_launch<true>(H, ss, nss, ln_w, eps, W_gate_up, nullptr, act, M, F, K, ldh, (int64_t)F, (F + 7) / 8, stream);
+}
+
+// ---- the same three entries on 8-bit weights (e4m3 codes + a power-of-two scale per row, RowsW8): bit for bit the 16-bit entry on the
+// dequantised weight.  A shape outside M <= 16, K % 256 == 0 and the LDS cap is VDD_ERR_UNSUPPORTED: the caller runs the 16-bit twin.
+VDD_HIDDEN int VDD_IMPL(vdd_skinny_gemm_resid_ss_w8)(const void* X, const void* W8, const float* w_scale, const void* R, void* Y, float* ss_out, int M,
+                                int N, int K, int64_t ldx, int64_t ldr, int64_t ldy, void* stream) {
+    if (M <= 0 || N <= 0) return VDD_OK;
+    if (!X || !W8 || !w_scale || !R || !Y || !ss_out || (ldx % 8) != 0) return VDD_ERR_INVALID_ARG;
+    if (M > 16 || K <= 0 || K % 256 != 0) return VDD_ERR_UNSUPPORTED;
+    resid_ss_launch<RowsW8>(X, W8, w_scale, R, Y, ss_out, M, N, K, ldx, ldr, ldy, stream);
+    return ok(hipSuccess);
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_skinny_gemm_normed_w8)(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W8,
+                              const float* w_scale, void* Y, int M, int N, int K, int64_t ldh, int64_t ldy, void* stream) {
+    if (M <= 0 || N <= 0) return VDD_OK;
+    if (!H || !ss || nss <= 0 || (nss % 4) != 0 || !ln_w || !W8 || !w_scale || !Y || (ldh % 8) != 0) return VDD_ERR_INVALID_ARG;
+    if (M > 16 || K <= 0 || K % 256 != 0) return VDD_ERR_UNSUPPORTED;
+    return normed_launch<false, RowsW8>(H, ss, nss, ln_w, eps, W8, w_scale, Y, M, N, K, ldh, ldy, (N + 15) / 16, stream);
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_skinny_swiglu_normed_w8)(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W8_gate_up,
+                                const float* w_scale, void* act, int M, int F, int K, int64_t ldh, void* stream) {
+    if (M <= 0 || F <= 0) return VDD_OK;
+    if (!H || !ss || nss <= 0 || (nss % 4) != 0 || !ln_w || !W8_gate_up || !w_scale || !act || (ldh % 8) != 0) return VDD_ERR_INVALID_ARG;
+    if (M > 16 || K <= 0 || K % 256 != 0) return VDD_ERR_UNSUPPORTED;
+    return normed_launch<true, RowsW8>(H, ss, nss, ln_w, eps, W8_gate_up, w_scale, act, M, F, K, ldh, (int64_t)F, (F + 7) / 8, stream);
 }
 VDD_HIDDEN int VDD_IMPL(vdd_skinny_swiglu)(const void* X, const void* W_gate_up, void* act, int M, int F, int K, int64_t ldx, void* stream) {
     return skinny_swiglu_launch(X, W_gate_up, act, M, F, K, ldx, stream);

@@ -27,6 +27,7 @@ The command-line defaults differ per driver ON PURPOSE (each follows its referen
 """
 from __future__ import annotations
 
+import argparse
 import contextlib
 import json
 import os
@@ -215,8 +216,14 @@ def add_common_args(ap, help: Optional[dict] = None, dtype: str = "float16", **d
         default = defaults.pop(dest, default)
         ap.add_argument(flag, type=typ, help=(help or {}).get(dest), **(dict(required=True) if default is REQUIRED else dict(default=default)))
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default=dtype, help="model dtype (the reference loads LLaVA / Vicuna in fp16, builder.py:40)")
+    ap.add_argument("--load-8bit", action="store_true", default=argparse.SUPPRESS, help="e4m3 weight storage for the few-row decode step (builder.py:26-31 load_8bit; VddLlavaEngine(load_8bit=True))")
     if defaults:
         raise TypeError(f"not common options: {sorted(defaults)}")
+
+
+def load_kw(a) -> dict:
+    """The loader / engine keywords the common options select: `load_8bit=True` after --load-8bit, nothing otherwise."""
+    return dict(load_8bit=True) if getattr(a, "load_8bit", False) else {}
 
 
 def add_script_args(ap, conv_mode: str = "llava_v1") -> None:

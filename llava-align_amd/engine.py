@@ -219,13 +219,42 @@ class LlavaWeights:
             w.t[p + "fc2"], w.t[p + "b2"] = get(vs, q + "mlp.fc2.weight"), get(vs, q + "mlp.fc2.bias")
         return w
 
+    W8_NAMES = ("wqkv", "wo", "wgu", "wd")
+
+    def quantize_lm_w8(self) -> "LlavaWeights":
+        """load_8bit: every decoder layer's wqkv / wo / wgu / wd and lm_head (padded to a multiple of 8 rows, as LanguageModel pads it)
+        become their e4m3 quantisation (ops.quantize_w8): t[name] <- w16, the dequantised 16-bit weight that every kernel of the package
+        runs as before, and t[name + ".w8"] / t[name + ".w8s"] <- the codes and the power-of-two row scales that the few-row decode step
+        streams instead.  Embeddings, norms, biases, vision tower and projector stay as they are.  Call it before the engine (its
+        LanguageModel) is built over these weights; a second call changes nothing."""
+        t, lm = self.t, self.cfg.lm
+        names = [f"l{i}.{n}" for i in range(lm.n_layers) for n in self.W8_NAMES] + ["lm_head"]
+        for name in names:
+            if name + ".w8" in t:
+                continue
+            w = t[name]
+            if name == "lm_head" and w.shape[0] % 8 != 0:
+                w = torch.nn.functional.pad(w, (0, 0, 0, (-w.shape[0]) % 8))
+            if w.shape[1] % ops.W8_GROUP != 0:
+                continue                                            # no 8-bit row order for this width: the weight stays 16-bit
+            codes, scale, w16 = ops.quantize_w8(w)
+            m, _e = torch.frexp(scale)
+            assert bool((m == 0.5).all()), "8-bit row scales are powers of two"
+            t[name], t[name + ".w8"], t[name + ".w8s"] = w16[:t[name].shape[0]].contiguous(), codes, scale
+        return self
+
+    def w8(self, name: str):
+        """(codes, scale) of weight `name` for the ops wrappers' `w8=`, or None for a weight that was not quantised."""
+        c = self.t.get(name + ".w8")
+        return None if c is None else (c, self.t[name + ".w8s"])
+
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.t.values())
 
     def lm_stream_bytes(self) -> int:
-        """Bytes a decode step must stream: every LM weight except the embedding table (gathered)."""
+        """Bytes a decode step must stream as 16-bit weights: every LM weight except the embedding table (gathered)."""
         return sum(t.numel() * 2 for k, t in self.t.items()
-                   if (k.startswith("l") and k[1].isdigit()) or k in ("norm", "lm_head"))
+                   if ((k.startswith("l") and k[1].isdigit()) or k in ("norm", "lm_head")) and not k.endswith((".w8", ".w8s")))
 
 
 def rope_table(lm: LMConfig, device) -> torch.Tensor:
@@ -496,7 +525,8 @@ class LanguageModel:
     def _head(self, a=None, resid=None, ss=None):
         """Final norm (fused for a few rows) + output projection -> [rows, V] logits."""
         c = self.cfg
-        y = ops.linear(a, self.lm_head) if a is not None else ops.linear_normed(resid, ss, self.w.t["norm"], c.eps, self.lm_head)
+        y = ops.linear(a, self.lm_head) if a is not None else ops.linear_normed(resid, ss, self.w.t["norm"], c.eps, self.lm_head,
+                                                                                w8=self.w.w8("lm_head"))
         return y if y.shape[1] == c.vocab else y[:, :c.vocab]
 
     @torch.no_grad()
@@ -571,8 +601,9 @@ class LanguageModel:
         projections write the residual stream themselves (+ per-block sums of squares of its rows), and the projections that read a
         normalised input (qkv, gate/up, lm_head) normalise it as it loads (ops.linear_resid_ss / linear_normed): the two 6.8-us
         RMSNorm launches of a layer - a tenth of a one-question step - are gone; only layer 0 normalises the embeddings with the
-        stand-alone kernel."""
-        c, t = self.cfg, self.w.t
+        stand-alone kernel.  Weights quantised by LlavaWeights.quantize_lm_w8 are streamed as 8-bit codes while ops.W8_DECODE is on
+        (layer 0's qkv, a plain ops.linear, reads w16): the same bits either way."""
+        c, t, w8 = self.cfg, self.w.t, self.w.w8
         H, Hkv, D = c.n_heads, c.n_kv_heads, c.head_dim
         ss = None
         for i in range(c.n_layers):
@@ -581,12 +612,12 @@ class LanguageModel:
             if ss is None:
                 qkv = ops.linear(ops.rmsnorm(resid, t[p + "ln1"], c.eps), t[p + "wqkv"], bias=bias)
             else:
-                qkv = ops.linear_normed(resid, ss, t[p + "ln1"], c.eps, t[p + "wqkv"], bias=bias)
+                qkv = ops.linear_normed(resid, ss, t[p + "ln1"], c.eps, t[p + "wqkv"], bias=bias, w8=w8(p + "wqkv"))
             att = ops.decode_attention_fused(qkv, pos, cpos, slot, self.cs, kv.ko[i], kv.vo[i], attn_rows, H, Hkv, D,
                                              k_prefix=kv.kp[i], v_prefix=kv.vp[i])
-            resid, ss = ops.linear_resid_ss(att, t[p + "wo"], resid)
-            act = ops.swiglu_linear_normed(resid, ss, t[p + "ln2"], c.eps, t[p + "wgu"])
-            resid, ss = ops.linear_resid_ss(act, t[p + "wd"], resid)
+            resid, ss = ops.linear_resid_ss(att, t[p + "wo"], resid, w8=w8(p + "wo"))
+            act = ops.swiglu_linear_normed(resid, ss, t[p + "ln2"], c.eps, t[p + "wgu"], w8=w8(p + "wgu"))
+            resid, ss = ops.linear_resid_ss(act, t[p + "wd"], resid, w8=w8(p + "wd"))
         return self._head(resid=resid, ss=ss)
 
     @torch.no_grad()
@@ -614,7 +645,7 @@ class LanguageModel:
             forms = lambda: dict(fused=lambda i: self._decode_step_few_rows(resid.clone(), pos, cpos, slot, attn_rows, kv),
                                  plain=lambda i: self._decode_layers(resid.clone(), pos, cpos, slot, attn_rows, kv, None, workspace),
                                  device=self.w.device, n_rot=1, iters=3)
-            if ops.norm_fused_pays(M, c.d, self.w.dtype, forms):
+            if ops.norm_fused_pays(M, c.d, self.w.dtype, forms, w8=ops.W8_DECODE and self.w.w8("l0.wo") is not None):
                 return self._decode_step_few_rows(resid, pos, cpos, slot, attn_rows, kv)
         return self._decode_layers(resid, pos, cpos, slot, attn_rows, kv, grouping, workspace)
 
@@ -1028,9 +1059,16 @@ class VddLlavaEngine:
 
     def __init__(self, cfg: LlavaConfig | str = "llava-1.5-7b", weights: Optional[LlavaWeights] = None, device="cuda:0",
                  seed: int = 0, max_questions: int = 64, t_max: int = 0, use_graph: bool = True, lm_head_gain: float = 1.0,
-                 dtype: Optional[torch.dtype] = None):
+                 dtype: Optional[torch.dtype] = None, load_8bit: bool = False, load_4bit: bool = False):
         """dtype: torch.bfloat16 (default; BASELINE config #2) or torch.float16 - the dtype every released driver of the reference loads
-        its checkpoint in (builder.py:40, llava_calibrate.py:163).  With `weights` given, their dtype is the engine's."""
+        its checkpoint in (builder.py:40, llava_calibrate.py:163).  With `weights` given, their dtype is the engine's.
+        load_8bit (builder.py:26-31): the language model's projection weights and lm_head are quantised to e4m3 codes with power-of-two
+        row scales (LlavaWeights.quantize_lm_w8, in place - `weights` included): the engine then runs the dequantised 16-bit model
+        everywhere, and the few-row decode step streams the codes - half the bytes, the same bits.  This is weight-only e4m3 STORAGE,
+        not bitsandbytes' LLM.int8 arithmetic; the 16-bit copy is kept for the prefill GEMM and every other path, so weight memory grows
+        by the codes (+6.6 GB at 7B)."""
+        if load_4bit:
+            raise NotImplementedError("load_4bit: this package has no 4-bit weight form; load_8bit=True (e4m3 weight streaming) is the quantised option")
         self.cfg = preset(cfg) if isinstance(cfg, str) else cfg
         self.device = torch.device(device)
         if weights is not None and dtype is not None and weights.dtype != dtype:
@@ -1039,6 +1077,8 @@ class VddLlavaEngine:
         if self.dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"model dtype must be torch.bfloat16 or torch.float16 (got {self.dtype}): the kernels are built for those two")
         self.w = weights if weights is not None else LlavaWeights.random(self.cfg, self.device, seed, lm_head_gain=lm_head_gain, dtype=self.dtype)
+        if load_8bit:
+            self.w.quantize_lm_w8()
         self.vit = VisionTower(self.w)
         self.vit.use_graph = use_graph
         self.lm = LanguageModel(self.w)
@@ -1380,7 +1420,7 @@ class VddLlavaEngine:
         ctr0 = self._philox_counter(seed)
         eos_t = h2d_long(dev, eos_token_id) if eos_token_id is not None else None
         cfgkey = (Q, nb, max_new_tokens, alpha, beta, warp.t, warp.k, warp.p, use_cd, use_dd, use_dd_unk, cd_greedy,
-                  tuple(eos_token_id) if eos_token_id is not None else None, pad_token_id, output_scores, ops.GEMM_BATCH_INVARIANT)
+                  tuple(eos_token_id) if eos_token_id is not None else None, pad_token_id, output_scores, ops.GEMM_BATCH_INVARIANT, ops.W8_DECODE)
         cpi = ops.prefix_chunks_per_item(grp, lm.n_heads)
         n_groups, n_items = len(grp), len(ops.prefix_work_items(grp, cpi))
         cfgkey = cfgkey + (n_groups, n_items, cpi, proc_key)
@@ -1615,7 +1655,7 @@ class VddLlavaEngine:
         eos_t = h2d_long(dev, eos_token_id)
         ctr0 = self._philox_counter(seed)
         cfgkey = ("list", Qc, nb, max_new_tokens, alpha, beta, warp.t, warp.k, warp.p, use_dd, use_dd_unk, vcd, cd_greedy, tuple(eos_token_id), pad_token_id,
-                  ops.GEMM_BATCH_INVARIANT) + (("paged",) if paged_kv else ())
+                  ops.GEMM_BATCH_INVARIANT, ops.W8_DECODE) + (("paged",) if paged_kv else ())
         tail = dict(alpha=alpha, beta=beta, warp=warp, contrast=contrast, is_vcd=vcd, both=(use_dd and use_dd_unk), greedy=cd_greedy, eos_t=eos_t,
                     pad=pad_token_id, output_scores=False, n_groups=0, n_items=0, cpi=1, proc={}, admit=True)
         run = self._runner(cfgkey, Qc, nb, max_new_tokens, tail, kv)

@@ -24,7 +24,7 @@ import torch
 
 from . import calibrate as C
 from . import shard
-from .driver_common import (ShardedRun, add_common_args, add_script_args, answer_text, eos_set, finish_distributed, plain_kw, read_questions, setting_kw,
+from .driver_common import (ShardedRun, add_common_args, load_kw, add_script_args, answer_text, eos_set, finish_distributed, plain_kw, read_questions, setting_kw,
                             sweep_result, sweep_settings, write_jsonl)
 from .engine import IMAGE_TOKEN_INDEX, VddLlavaEngine
 from .vcd_add_noise import add_diffusion_noise
@@ -253,14 +253,14 @@ def main(argv=None):
     questions = read_questions(a.question_file)
     gen_kw = dict(use_dd=a.use_dd, use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta)
     if a.arch == "llava":
-        eng, tok, proc = K.load_llava(a.model_path, device, dtype=dtype, vision_tower=a.vision_tower, fallback_preset=a.preset)
+        eng, tok, proc = K.load_llava(a.model_path, device, dtype=dtype, vision_tower=a.vision_tower, fallback_preset=a.preset, **load_kw(a))
         build = llava_mme_inputs(lambda prompt: K.tokenizer_image_token(tok, prompt), lambda name: K.clip_preprocess(proc, os.path.join(a.image_folder, name)),
                                  unk_token_id=tok.unk_token_id if tok.unk_token_id is not None else 0)
         decode = lambda ids: tok.decode(ids, skip_special_tokens=True)
         run_kw = dict(eos_token_id=tok.eos_token_id, pad_token_id=tok.pad_token_id or 0, stop_str="</s>", max_new_tokens=a.max_new_tokens or 128,
                       noise_step=a.noise_step if a.use_cd else None)
     else:
-        eng, tok, _model, embed_prompt = K.load_qwen(a.model_path, device, dtype=dtype, native_visual=a.native_visual)      # run_qwen.py:176-186: the ViT reads the path in the prompt
+        eng, tok, _model, embed_prompt = K.load_qwen(a.model_path, device, dtype=dtype, native_visual=a.native_visual, **load_kw(a))      # run_qwen.py:176-186: the ViT reads the path in the prompt
         build = qwen_mme_inputs(embed_prompt, lambda f: os.path.join(a.image_folder, f))
         decode = lambda ids: tok.decode(ids, skip_special_tokens=True)
         run_kw = dict(eos_token_id=tok.eod_id, pad_token_id=tok.eod_id, max_new_tokens=a.max_new_tokens or 20, min_new_tokens=1)      # run_qwen.py:194-197

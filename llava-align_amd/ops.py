@@ -39,6 +39,9 @@ _SIGS = {
     "vdd_skinny_gemm_resid_ss": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _P],
     "vdd_skinny_gemm_normed": [_P, _P, _I, _P, _F, _P, _P, _I, _I, _I, _L, _L, _I, _P],
     "vdd_skinny_swiglu_normed": [_P, _P, _I, _P, _F, _P, _P, _I, _I, _I, _L, _I, _P],
+    "vdd_skinny_gemm_resid_ss_w8": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _P],
+    "vdd_skinny_gemm_normed_w8": [_P, _P, _I, _P, _F, _P, _P, _P, _I, _I, _I, _L, _L, _I, _P],
+    "vdd_skinny_swiglu_normed_w8": [_P, _P, _I, _P, _F, _P, _P, _P, _I, _I, _I, _L, _I, _P],
     "vdd_rope_kv_write_paged": [_P] * 9 + [_I, _I, _I, _I, _L, _I, _I, _I, _I, _P],
     "vdd_decode_attention_paged": [_P] * 9 + [_I, _I, _I, _I, _L, _I, _I, _I, _L, _I, _I, _F, _I, _P],
     "vdd_kv_pages_scatter": [_P] * 7 + [_I, _I, _I, _I, _L, _I, _L, _I, _I, _I, _I, _P],
@@ -254,7 +257,7 @@ FORCE_FORM = {}             # tests / probes: kind ("linear", "to_norm", "swiglu
 FORCE_LAYER_FORM = None     # tests / probes: "fused" | "plain" for every row count the fused layer serves
 
 
-def norm_fused_pays(M: int, d: int, dtype=torch.bfloat16, time_forms=None) -> bool:
+def norm_fused_pays(M: int, d: int, dtype=torch.bfloat16, time_forms=None, w8: bool = False) -> bool:
     """Does a decode step of M rows take the norm-fused five-launch layer (RMSNorms inside the projections around them) or the
     seven-launch layer (stand-alone norms, the projections in whatever form `_pick_form` measured)?  Measured once per (rows, d, dtype):
     `time_forms()` -> {"fused": fn(i), "plain": fn(i), "device", "n_rot", "iters"}: the engine passes the WHOLE decode step in either form
@@ -262,12 +265,14 @@ def norm_fused_pays(M: int, d: int, dtype=torch.bfloat16, time_forms=None) -> bo
     decide - profiles/r06_layer_form_probe.jsonl); without them - or under capture, or with the tuner off - the shape-generic fallback:
     up to 8 rows.  What the measurement finds on the MI355X (tools/fused_band_probe.py, profiles/r05_*): 7B widths fused
     everywhere up to 16 rows except 9 - 12 (the normalise-once kernels change their block plan at 9 rows); d = 5120 only up to 7 rows
-    (above, its d-wide projections are faster as split-K slabs, which need the stand-alone norms).  Never in batch-invariant mode."""
+    (above, its d-wide projections are faster as split-K slabs, which need the stand-alone norms).  Never in batch-invariant mode.
+    w8: the fused layer streams 8-bit weight codes (quantize_w8) - another kernel set, measured under a key of its own (8 in the fourth
+    slot) and never read from the 16-bit choices."""
     if GEMM_BATCH_INVARIANT or M > norm_fused_rows(d):
         return False
     if FORCE_LAYER_FORM is not None:
         return FORCE_LAYER_FORM == "fused"
-    key = ("layer", M, d, 0, _MODEL_DT[dtype])
+    key = ("layer", M, d, 8 if w8 else 0, _MODEL_DT[dtype])
     got = _form_choice.get(key)
     if got is None and time_forms is not None and GEMM_AUTOTUNE and not torch.cuda.is_current_stream_capturing():
         tf = time_forms()                                  # built only when a measurement is really due
@@ -284,35 +289,163 @@ def norm_fused_rows(d: int) -> int:
     return min(NORM_FUSED_MAX_M, (142 * 1024) // (2 * d)) if d % 256 == 0 and d <= 8192 else 0
 
 
-def linear_resid_ss(x, w, resid, out=None, ss=None):
+# ---- 8-bit weights of the few-row decode step (load_8bit): OCP e4m3fn codes + one power-of-two fp32 scale per output row.  A code
+# times a power of two is a bf16 / fp16 value, so the quantised model IS a 16-bit model (w16 = code * scale, exact) that every kernel
+# of the package runs unchanged; the three projections of the norm-fused layer also read it as codes - half the bytes of the step's
+# weight stream - and return, bit for bit, what their 16-bit twins return on w16 (csrc/vdd_w8.h).
+W8_DECODE = True            # False: the few-row step streams w16 even where codes exist (the same model, the same bits)
+W8_GROUP = 64               # storage order of a row's codes: include/vdd_hip.h, "8-bit weight rows"
+_VDD_ERR_UNSUPPORTED = -2
+_w8_launches = [0]
+
+
+@contextlib.contextmanager
+def w8_decode(on: bool = True):
+    """with ops.w8_decode(False): ...  -  the 16-bit twins on w16 for the duration (the captured steps are keyed by the switch)."""
+    global W8_DECODE
+    prev = W8_DECODE
+    W8_DECODE = bool(on)
+    try:
+        yield
+    finally:
+        W8_DECODE = prev
+
+
+def w8_launches() -> int:
+    """8-bit-weight kernel launches issued by this process so far (a launch recorded into a graph counts once, at capture)."""
+    return _w8_launches[0]
+
+
+def _e4m3_values() -> torch.Tensor:
+    """fp32 value of every e4m3fn code (0x7F / 0xFF, the NaNs, as NaN)."""
+    vals = []
+    for c in range(256):
+        e, m = (c >> 3) & 15, c & 7
+        v = float("nan") if (c & 0x7F) == 0x7F else (m * 2.0 ** -9 if e == 0 else (1 + m / 8.0) * 2.0 ** (e - 7))
+        vals.append(-v if c & 0x80 else v)
+    return torch.tensor(vals, dtype=torch.float32)
+
+
+def w8_pack(codes: torch.Tensor) -> torch.Tensor:
+    """[N, K] codes in element order -> the kernels' storage order: inside every aligned group of 64 K-elements the 8 elements a lane
+    group g = 0..3 owns in k-step 2b (k = 64b + 8g ...) sit next to its 8 of k-step 2b + 1 (k = 64b + 32 + 8g ...): one 16-byte load
+    per lane covers two MFMA k-steps and a row stays contiguous."""
+    N, K = codes.shape
+    if K % W8_GROUP != 0:
+        raise ValueError(f"w8_pack: K = {K} is not a multiple of {W8_GROUP}")
+    return codes.reshape(N, K // 64, 2, 4, 8).transpose(2, 3).reshape(N, K).contiguous()
+
+
+def w8_unpack(packed: torch.Tensor) -> torch.Tensor:
+    N, K = packed.shape
+    if K % W8_GROUP != 0:
+        raise ValueError(f"w8_unpack: K = {K} is not a multiple of {W8_GROUP}")
+    return packed.reshape(N, K // 64, 4, 2, 8).transpose(2, 3).reshape(N, K).contiguous()
+
+
+def w8_dequantize(codes: torch.Tensor, scale: torch.Tensor, dtype) -> torch.Tensor:
+    """Packed codes + row scales -> w16 (exact in bf16 and fp16)."""
+    lut = _e4m3_values().to(codes.device)
+    return (lut[w8_unpack(codes).long()] * scale[:, None]).to(dtype)
+
+
+def quantize_w8(w: torch.Tensor):
+    """[N, K] bf16 / fp16 weight (any device) -> (codes uint8 [N, K] in storage order, scale fp32 [N], w16 [N, K]).  Per row:
+    scale = 2^e with e the smallest integer that brings the row's largest magnitude to <= 448 (e >= -15 for fp16, so that the
+    smallest code, 2^-9, still lands on an fp16 value; an all-zero row: e = 0); code = RNE(w / scale) to e4m3fn - never a NaN code;
+    w16 = code * scale, exact in w's dtype.  e4m3 carries its own exponent: the scale only positions the range, it costs no precision."""
+    if w.dim() != 2 or w.dtype not in _MODEL_DT:
+        raise ValueError("quantize_w8 takes a [N, K] bf16 or fp16 weight")
+    wf = w.float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_w8: non-finite weight")
+    a = wf.abs().amax(dim=1)
+    m, ex = torch.frexp(a)                                           # a = m 2^ex, m in [0.5, 1);  448 = 0.875 * 2^9
+    e = torch.where(m <= 0.875, ex - 9, ex - 8)
+    e = torch.where(a == 0, torch.zeros_like(e), e)
+    if w.dtype == torch.float16:
+        e = e.clamp(min=-15)
+    x = torch.ldexp(wf, -e[:, None])                                 # exact: |x| <= 448
+    ax = x.abs()
+    _, xe = torch.frexp(ax)
+    q = torch.ldexp(torch.ones_like(ax), (xe - 4).clamp(min=-9))     # the e4m3 spacing at |x|: 2^(floor(log2 |x|) - 3), subnormals 2^-9
+    r = (torch.round(ax / q) * q).clamp(max=448.0)                   # torch.round: half to even = RNE on the mantissa
+    rm, rex = torch.frexp(r)
+    normal = r >= 2.0 ** -6
+    mag = torch.where(normal, ((rex + 6) << 3) + ((rm * 16).to(torch.int32) - 8), (r * 512).to(torch.int32))
+    codes = (mag | ((x < 0) | ((x == 0) & torch.signbit(x))).to(torch.int32) << 7).to(torch.uint8)
+    scale = torch.ldexp(torch.ones_like(a), e)
+    w16f = torch.where(x < 0, -r, r) * scale[:, None]
+    w16 = w16f.to(w.dtype)
+    if not bool(torch.isfinite(w16).all()):
+        raise ValueError("quantize_w8: a quantised weight leaves the range of " + str(w.dtype))
+    return w8_pack(codes), scale, w16
+
+
+def _w8_args(w, w8):
+    """The (codes, scale) of weight `w` if this call streams codes: the switch is on and the pair was built for w's shape."""
+    if w8 is None or not W8_DECODE:
+        return None
+    codes, scale = w8
+    if codes.dtype != torch.uint8 or scale.dtype != torch.float32 or tuple(codes.shape) != tuple(w.shape) or scale.shape[0] != w.shape[0] \
+            or not codes.is_contiguous() or not scale.is_contiguous() or codes.device != w.device:
+        raise ValueError("w8 = (uint8 codes [N, K] from quantize_w8, fp32 scale [N]) of the same weight")
+    return codes, scale
+
+
+def _w8_done(rc) -> bool:
+    """Status of an 8-bit entry: launched (counted), or a shape it does not serve - the caller runs the 16-bit twin on w16, the same
+    model and the same bits."""
+    if rc == _VDD_ERR_UNSUPPORTED:
+        return False
+    _lib.check(rc)
+    _w8_launches[0] += 1
+    return True
+
+
+def linear_resid_ss(x, w, resid, out=None, ss=None, w8=None):
     """h = bf16(bf16(x w^T) + resid) (the new residual stream) and ss [M, N/16] fp32: per-block partial sums of squares of h's rows,
-    for linear_normed / swiglu_linear_normed.  M <= NORM_FUSED_MAX_M."""
+    for linear_normed / swiglu_linear_normed.  M <= NORM_FUSED_MAX_M.  w8: (codes, scale) of w (quantize_w8) - streamed instead."""
     dt = _dt(x, w, resid)
     M, K = x.shape
     N = w.shape[0]
     out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
     ss = torch.empty(M, (N + 15) // 16, dtype=torch.float32, device=x.device) if ss is None else ss
+    q = _w8_args(w, w8)
+    if q is not None and _w8_done(_lib_ready().vdd_skinny_gemm_resid_ss_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), resid.data_ptr(),
+                                                                            out.data_ptr(), ss.data_ptr(), M, N, K, x.stride(0),
+                                                                            resid.stride(0), out.stride(0), dt, _st(x))):
+        return out, ss
     _lib.check(_lib_ready().vdd_skinny_gemm_resid_ss(x.data_ptr(), w.data_ptr(), resid.data_ptr(), out.data_ptr(), ss.data_ptr(), M, N, K,
                                                      x.stride(0), resid.stride(0), out.stride(0), dt, _st(x)))
     return out, ss
 
 
-def linear_normed(h, ss, ln_w, eps, w, out=None, bias=None):
+def linear_normed(h, ss, ln_w, eps, w, out=None, bias=None, w8=None):
     """rmsnorm(h; ln_w, eps) @ w^T with the normalisation done as h's fragments load (h, ss from linear_resid_ss)."""
     dt = _dt(h, w, ln_w)
     M, K = h.shape
     N = w.shape[0]
     out = torch.empty(M, N, dtype=h.dtype, device=h.device) if out is None else out
-    _lib.check(_lib_ready().vdd_skinny_gemm_normed(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, w.data_ptr(), out.data_ptr(),
-                                                   M, N, K, h.stride(0), out.stride(0), dt, _st(h)))
+    q = _w8_args(w, w8)
+    if not (q is not None and _w8_done(_lib_ready().vdd_skinny_gemm_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps,
+                                                                               q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, N, K,
+                                                                               h.stride(0), out.stride(0), dt, _st(h)))):
+        _lib.check(_lib_ready().vdd_skinny_gemm_normed(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, w.data_ptr(), out.data_ptr(),
+                                                       M, N, K, h.stride(0), out.stride(0), dt, _st(h)))
     return bias_act(out, bias, out=out) if bias is not None else out
 
 
-def swiglu_linear_normed(h, ss, ln_w, eps, w_gate_up, out=None):
+def swiglu_linear_normed(h, ss, ln_w, eps, w_gate_up, out=None, w8=None):
     dt = _dt(h, w_gate_up, ln_w)
     M, K = h.shape
     F = w_gate_up.shape[0] // 2
     out = torch.empty(M, F, dtype=h.dtype, device=h.device) if out is None else out
+    q = _w8_args(w_gate_up, w8)
+    if q is not None and _w8_done(_lib_ready().vdd_skinny_swiglu_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps,
+                                                                            q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, F, K,
+                                                                            h.stride(0), dt, _st(h))):
+        return out
     _lib.check(_lib_ready().vdd_skinny_swiglu_normed(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, w_gate_up.data_ptr(),
                                                      out.data_ptr(), M, F, K, h.stride(0), dt, _st(h)))
     return out

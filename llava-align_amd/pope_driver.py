@@ -23,7 +23,7 @@ import torch
 
 from . import calibrate as C
 from . import shard
-from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, answer_text, cut_at_eos, distinct, eos_set, finish_distributed,  # noqa: F401 (cut_at_eos: re-exported)
+from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, load_kw, answer_text, cut_at_eos, distinct, eos_set, finish_distributed,  # noqa: F401 (cut_at_eos: re-exported)
                             plain_kw, pope_scores_for, read_questions, to_all_rows, write_jsonl)
 from .engine import IMAGE_TOKEN_INDEX, VddLlavaEngine
 from .vcd_add_noise import add_diffusion_noise
@@ -182,7 +182,7 @@ def main(argv=None):
     a = _parser().parse_args(argv)
     from .checkpoint import clip_preprocess, load_llava, tokenizer_image_token
     rank, world, device = shard.init_from_env()
-    eng, tok, proc = load_llava(a.model_path, device, dtype=getattr(torch, a.dtype), vision_tower=a.vision_tower, fallback_preset=a.preset)
+    eng, tok, proc = load_llava(a.model_path, device, dtype=getattr(torch, a.dtype), vision_tower=a.vision_tower, fallback_preset=a.preset, **load_kw(a))
     encode = lambda text, with_image: tokenizer_image_token(tok, llava_v1_prompt(text, with_image))
 
     questions = read_questions(a.question_file)

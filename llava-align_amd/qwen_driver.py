@@ -29,7 +29,7 @@ import torch
 
 from . import calibrate as C
 from . import shard
-from .driver_common import (ShardedRun, add_common_args, add_script_args, answer_text, chunk_of, distinct, eos_set, finish_distributed, load_distinct_images,
+from .driver_common import (ShardedRun, add_common_args, load_kw, add_script_args, answer_text, chunk_of, distinct, eos_set, finish_distributed, load_distinct_images,
                             plain_kw, pope_scores_for, read_questions, setting_kw, sweep_result, sweep_settings, to_all_rows, write_jsonl)
 from .engine import VddLlavaEngine
 
@@ -209,7 +209,7 @@ def main(argv=None):
     a = _parser().parse_args(argv)
     from . import checkpoint as K
     rank, world, device = shard.init_from_env()
-    eng, tok, model, embed_prompt = K.load_qwen(a.model_path, device, dtype=getattr(torch, a.dtype), native_visual=a.native_visual)
+    eng, tok, model, embed_prompt = K.load_qwen(a.model_path, device, dtype=getattr(torch, a.dtype), native_visual=a.native_visual, **load_kw(a))
     questions = chunk_of(read_questions(a.question_file), a)
 
     def load_image(name):                                      # qwen_calibrate.py:100-101

@@ -16,7 +16,7 @@ from typing import Callable, List, Optional, Sequence
 import torch
 
 from . import shard
-from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, add_script_args, answer_text, chunk_of, eos_set, finish_distributed, load_distinct_images, read_questions,
+from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, load_kw, add_script_args, answer_text, chunk_of, eos_set, finish_distributed, load_distinct_images, read_questions,
                             write_jsonl)
 from .engine import VddLlavaEngine
 from .vcd_add_noise import add_diffusion_noise
@@ -107,7 +107,7 @@ def main(argv=None):
     a = _parser().parse_args(argv)
     from . import checkpoint as K
     rank, world, device = shard.init_from_env()
-    eng, tok, proc = K.load_llava(a.model_path, device, dtype=getattr(torch, a.dtype), vision_tower=a.vision_tower, fallback_preset=a.preset)
+    eng, tok, proc = K.load_llava(a.model_path, device, dtype=getattr(torch, a.dtype), vision_tower=a.vision_tower, fallback_preset=a.preset, **load_kw(a))
     questions = chunk_of(read_questions(a.question_file), a)
     runs = [("default", 1.0, None, None)]
     if a.naive:

@@ -1,0 +1,109 @@
+"""load_8bit: what the few-row decode step costs with 8-bit weight codes against 16-bit weights.
+
+    python tools/w8_step_probe.py [7b] [13b] [--layers N] [--out profiles/w8_decode_step.jsonl]
+        LLaVA-1.5-7B / 13B language-model shapes, bf16, rows 2, 3, 6, 12, 16 (questions x branches): ms per captured decode step from the
+        engine's HIP events (VddLlavaEngine.call_timing).  The two legs ALTERNATE in one process: "w16" is an unquantised engine with
+        ops.W8_DECODE off - the path of a build without this feature - and "w8" a load_8bit engine over the same random weights.  One JSON
+        line per (shape, rows) with the per-leg medians, the spread, the layer form each leg took and the bytes a step streams.
+    python tools/w8_step_probe.py --trace 7b
+        one leg-w8 and one leg-w16 decode at 2 rows, nothing else: the workload for a kernel trace taken in a run of its own,
+            timeout 600 rocprofv3 --kernel-trace --stats -d profiles/w8_trace -o w8 -- python tools/w8_step_probe.py --trace 7b
+        whose kernel stats go to profiles/w8_kernel_stats.csv.
+No GPU: the script fails (there is nothing to measure on a CPU)."""
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+
+from bench import pope_prompts
+from llava_align_amd import ops
+from llava_align_amd.engine import LlavaConfig, LlavaWeights, LMConfig, VddLlavaEngine, VisionConfig
+
+DEV = "cuda:0"
+SHAPES = {"7b": dict(d=4096, n_heads=32, n_kv_heads=32, head_dim=128, ffn=11008, vocab=32000, n_layers=32),
+          "13b": dict(d=5120, n_heads=40, n_kv_heads=40, head_dim=128, ffn=13824, vocab=32000, n_layers=40)}
+ROWS = {2: (1, 2), 3: (1, 3), 6: (3, 2), 12: (6, 2), 16: (8, 2)}          # rows -> (questions, branches)
+NEW, REPS = 48, 5
+
+
+def engines(name, layers):
+    kw = dict(SHAPES[name])
+    if layers:
+        kw["n_layers"] = layers
+    cfg = LlavaConfig(LMConfig(max_pos=1024, **kw), VisionConfig(layers=1), f"w8-probe-{name}")
+    w16 = LlavaWeights.random(cfg, DEV, seed=0, lm_head_gain=4.0)
+    w8 = LlavaWeights(cfg, DEV, w16.dtype)
+    w8.t = dict(w16.t)                                            # the same tensors; quantize_lm_w8 replaces the quantised entries only
+    return (VddLlavaEngine(cfg, weights=w16, device=DEV), VddLlavaEngine(cfg, weights=w8, device=DEV, load_8bit=True))
+
+
+def step_ms(eng, ids, kw, w8):
+    with ops.w8_decode(w8):
+        eng.call_log = []
+        eng.generate(ids, **kw)
+        t = eng.call_timing(eng.call_log[-1])
+        eng.call_log = None
+    return t["decode_ms"] / t["decode_steps"]
+
+
+def stream_bytes(eng, w8):
+    """Weight bytes one few-row step reads: 16-bit everywhere, or codes + scales where the fused layer streams them (layer 0's qkv stays 16-bit)."""
+    n = 0
+    for k, t in eng.w.t.items():
+        if k.endswith((".w8", ".w8s")) or not ((k.startswith("l") and k[1].isdigit()) or k in ("norm", "lm_head")):
+            continue
+        coded = w8 and eng.w.w8(k) is not None and k != "l0.wqkv"
+        n += t.numel() * (1 if coded else 2) + (t.shape[0] * 4 if coded else 0)
+    return n
+
+
+def main():
+    args = sys.argv[1:]
+    layers = int(args[args.index("--layers") + 1]) if "--layers" in args else 0
+    out = args[args.index("--out") + 1] if "--out" in args else None
+    names = [a for a in args if a in SHAPES] or list(SHAPES)
+    if not torch.cuda.is_available():
+        raise SystemExit("w8_step_probe: no GPU - nothing can be measured here")
+    for name in names:
+        e16, e8 = engines(name, layers)
+        lm = e16.cfg.lm
+        for rows, (Q, nb) in ROWS.items():
+            ids, imgs = pope_prompts(Q, per_img=1, seed=5, vocab=lm.vocab, image=e16.cfg.vision.image)
+            kw = dict(images=imgs, use_dd_unk=True, use_dd=nb == 3, cd_alpha=1.0, cd_beta=0.1, temperature=0.5, max_new_tokens=NEW, seed=1)
+            if "--trace" in args:
+                if rows == 2:
+                    for _ in range(2):
+                        step_ms(e8, ids, kw, True), step_ms(e16, ids, kw, False)
+                    torch.cuda.synchronize()
+                continue
+            for _ in range(2):                                    # warm-up: forms measured, steps captured
+                step_ms(e16, ids, kw, False), step_ms(e8, ids, kw, True)
+            t16, t8 = [], []
+            for _ in range(REPS):                                 # alternating legs
+                t16.append(step_ms(e16, ids, kw, False))
+                t8.append(step_ms(e8, ids, kw, True))
+            dt = ops._MODEL_DT[e16.dtype]
+            rec = dict(shape=name, layers=lm.n_layers, dtype="bf16", rows=rows, questions=Q, new_tokens=NEW, reps=REPS,
+                       w16_ms=round(statistics.median(t16), 4), w8_ms=round(statistics.median(t8), 4),
+                       w16_ms_all=[round(v, 4) for v in t16], w8_ms_all=[round(v, 4) for v in t8],
+                       w16_layer_form=ops._form_choice.get(("layer", rows, lm.d, 0, dt)), w8_layer_form=ops._form_choice.get(("layer", rows, lm.d, 8, dt)),
+                       w16_stream_gb=round(stream_bytes(e16, False) / 1e9, 3), w8_stream_gb=round(stream_bytes(e8, True) / 1e9, 3))
+            rec["speedup"] = round(rec["w16_ms"] / rec["w8_ms"], 3)
+            if Q == 1:
+                rec["w16_tok_s"], rec["w8_tok_s"] = round(1e3 / rec["w16_ms"], 1), round(1e3 / rec["w8_ms"], 1)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if out:
+                os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+                with open(out, "a") as f:
+                    f.write(line + "\n")
+        del e16, e8
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
