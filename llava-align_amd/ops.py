@@ -760,11 +760,12 @@ def gemm_source_fingerprint() -> str:
 
 def kernel_source_fingerprint() -> str:
     """What the in-tree FORM defaults are bound to: the sources of every kernel the forms choose between (the GEMM and the weight-streaming /
-    norm kernels)."""
+    norm kernels, 16-bit and 8-bit) and the headers they include.  csrc/vdd_decode_attention.hip is not among them: no form chooses between
+    attention kernels (both few-row layer forms call the same decode_attention_fused), so an attention edit leaves the measured choices valid."""
     import hashlib
     import os
     h = hashlib.sha256()
-    for f in ("vdd_gemm.hip", "vdd_llm_kernels.hip", "vdd_elem.h"):
+    for f in ("vdd_gemm.hip", "vdd_llm_kernels.hip", "vdd_llm_common.h", "vdd_elem.h", "vdd_w8.h"):
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", f)
         if not os.path.exists(path):
             return ""

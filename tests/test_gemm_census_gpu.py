@@ -310,7 +310,7 @@ def test_gemm_refuses_layouts_out_of_contract_before_any_launch(dt):
 # ------------------------------------------------------------------------------------------------ c. the weight-streaming family
 
 def skinny_form(M, N, K, slabs=False):
-    """the kernel vdd_skinny_gemm launches (skinny_gemm_launch in csrc/vdd_llm_kernels.hip), from the shape"""
+    """the kernel vdd_skinny_gemm launches (its dispatch in csrc/vdd_llm_kernels.hip), from the shape"""
     blocks = -(-N // 16)
     if M > 16 and not slabs and K % 256 == 0 and N > 8192:
         return "wide"
