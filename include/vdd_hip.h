@@ -225,6 +225,24 @@ int vdd_skinny_gemm_normed_w8(const void* H, const float* ss, int nss, const voi
 int vdd_skinny_swiglu_normed_w8(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W8_gate_up,
                                 const float* w_scale, void* act, int M, int F, int K, int64_t ldh, int dtype, void* hip_stream);
 
+/* The W-stream tiles of vdd_gemm (below) on 8-bit weight rows: Y[M,N] = epilogue(X[M,K] . (w_scale[n] * code(W8[n,k]))^T).
+ * W8 is [N, K] bytes ([2N, K] for VDD_GEMM_SWIGLU: gate rows, then up rows), contiguous rows in the storage order above, w_scale
+ * [N] ([2N]) fp32 powers of two, 16-byte aligned.  `config` has the bit layout of vdd_gemm's (tile id in bits 0-3 + 6-7, schedule in
+ * bits 4-5, schedule 3 = split-K slabs with S in bits 8-15 and Y = fp32 [S][M][N]); the workspace is vdd_gemm's.
+ * Bit-for-bit contract, as for the three entries above: the call returns what vdd_gemm with the same config returns on w16 = code *
+ * scale.  The codes reach LDS by the same LDS-DMA path (64 B per row and 64-deep K-tile), are widened in registers to the 16-bit
+ * MFMA fragments, feed the same MFMAs in the same order under the same schedule, work list and stream-K fix-up (partials travel
+ * unscaled), and w_scale[n] is multiplied onto the fp32 sum of column n behind the fix-up and before bias and the first rounding (for
+ * SwiGLU on gate and up with their own rows of w_scale; for slabs before the slab store).
+ * Served: tile ids 7-16 (the tiles with three or more K-tile buffers); epilogues VDD_GEMM_NONE, _BIAS, _SWIGLU (where vdd_gemm pairs
+ * gate and up for that tile), slabs on tile 8; K % 128 == 0; any M (the tiles are built for up to 256 rows: ops tunes them up to
+ * there).  Anything else returns VDD_ERR_UNSUPPORTED and launches
+ * nothing: the caller runs vdd_gemm on w16. */
+int vdd_gemm_w8(const void* X, const void* W8, const float* w_scale, void* Y, const void* bias,
+                int M, int N, int K, int64_t ldx, int64_t ldy,
+                int epilogue, int config, void* workspace, int64_t workspace_bytes,
+                int dtype, void* hip_stream);
+
 /* Row-batched projection GEMM, any M above the skinny regime (csrc/vdd_gemm.hip): Y[M,N] = epilogue(X[M,K] W[N,K]^T), bf16 in,
  * fp32 accumulate (32x32x16 MFMA, both operands LDS-DMA'd into swizzled LDS tiles, persistent stream-K over one workgroup
  * per CU), bf16 out.  K % 128 == 0, N % 4 == 0, ldx/ldw % 8 == 0 (elements).  Replaces the eager nn.Linear calls of HF

@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "vdd_elem.h"
+#include "vdd_w8.h"
 
 namespace {
 namespace VDD_ELEM_NS {
@@ -74,6 +75,7 @@ struct GemmArgs {
     int stage_out;               // Y rows are 16-byte aligned: the epilogue may store whole rows out of LDS
     float* slabs;                // split-K slab mode (slab_S > 0): fp32 partial products [slab_S][M][N], one (tile, K part) per workgroup, no
     int slab_S;                  // fix-up - the consumer (vdd_rmsnorm's delta_slabs) adds the slabs
+    const float* w_scale;        // 8-bit weight form (W8 instantiations): W holds e4m3 codes (ldw = bytes of a row), one power-of-two scale per W row
 };
 
 // K-tile buffers of a tile shape.  Two for the compute-bound shapes (tile t + 1 lands under the MFMAs of tile t).  The shapes the
@@ -97,15 +99,27 @@ constexpr int gemm_stages(int BM, int BN, int WM, int WN) {
     return 2;
 }
 
-template <int BM, int BN, int WM, int WN, int EPI>
+// The 8-bit weight form of a W stream (vdd_gemm_w8): W reaches LDS as e4m3 codes, 64 B per row and K-tile instead of 128, so a K-tile
+// buffer is BM * 128 + BN * 64 bytes and the freed LDS goes to more buffers - as many as fit beside the staging blocks, at most eight,
+// and never more than the 6-bit vmcnt counts (XJ + BN / 16 / NW LDS-DMA instructions per wave and K-tile).
+constexpr int gemm_stages_w8(int BM, int BN, int WM, int WN) {
+    const int n = (LDS_BYTES - gemm_staging_bytes(BN, WM, WN)) / (BM * 128 + BN * 64);
+    const int cap = 63 / ((BM / 8 + BN / 16) / (WM * WN)) + 1;
+    const int m = n > 8 ? 8 : n;
+    return m > cap ? cap : m;
+}
+
+template <int BM, int BN, int WM, int WN, int EPI, bool W8 = false>
 __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub: it drops a kernel whose body holds LDS-DMA builtins
     constexpr int NW = WM * WN, NT = NW * 64;
     constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 32, NI = TN / 32;
-    constexpr int XIMG = BM / 8, WIMG = BN / 8;            // 1-KiB LDS-DMA images (8 rows x 128 B) per K-tile
+    constexpr int XIMG = BM / 8, WIMG = W8 ? BN / 16 : BN / 8;   // 1-KiB LDS-DMA images (8 rows x 128 B; of codes: 16 rows x 64 B) per K-tile
     constexpr int XJ = XIMG / NW, WJ = WIMG / NW;          // images per wave
-    constexpr int BUF = (BM + BN) * 128;                   // bytes of one K-tile buffer
-    constexpr int NSTG = gemm_stages(BM, BN, WM, WN);      // K-tile buffers (> 2: a W stream, see the K pipeline below)
+    constexpr int WROW = W8 ? 64 : 128;                    // bytes of a W row in a K-tile buffer
+    constexpr int BUF = BM * 128 + BN * WROW;              // bytes of one K-tile buffer
+    constexpr int NSTG = W8 ? gemm_stages_w8(BM, BN, WM, WN) : gemm_stages(BM, BN, WM, WN);      // K-tile buffers (> 2: a W stream, see the K pipeline below)
+    static_assert(!W8 || (gemm_stages(BM, BN, WM, WN) >= 3 && NSTG >= 3), "the 8-bit weight form exists for the W-stream tiles only");
     constexpr int NMMA = NI * MI, NRD = NI + MI, NLD = XJ + WJ;
     // (the 192 x 256 tile of the decode batch only: down-projection 134 -> 120 us, o 57 -> 53 on cold weights; the 256 x 256 tile lost 5 - 12 % with it
     //  at 1,536 rows - 13 more spilled registers at the cliff - and gained nothing at prefill size, where the panels are L2 hits)
@@ -121,7 +135,14 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
     // fragment addresses: row * 128 + ((kk * 2 + (lane >> 5)) ^ ((lane >> 1) & 7)) * 16
     const int c0 = ((lane >> 5) ^ ((lane >> 1) & 7)) * 16;
     const int xrow = (wr * TM + (lane & 31)) * 128 + c0;
-    const int wrow = (BM + wc * TN + (lane & 31)) * 128 + c0;
+    // 8-bit weight form: a W row of the K-tile is 64 B = four 16-byte chunks, chunk g = 2 (kk % 2) + (lane >> 5) holding the lane half's
+    // 8 codes of k-step kk (low 8 bytes) and of k-step kk + 2 (high 8 bytes) - the storage order of ops.w8_pack as it is.  The chunk
+    // index is XOR-swizzled with (row >> 2) & 3: a ds_read_b128 lane group is 16 consecutive rows x one logical chunk, at byte
+    // row * 64 + ((g ^ (row >> 2) & 3)) * 16; row & 3 picks one of the four 64-byte quarters of the 256-byte bank window and the four
+    // rows that share a quarter (row, row + 4, + 8, + 12) differ in (row >> 2) & 3, so they take its four chunks: the 16 lanes cover all
+    // 16 sixteen-byte bank slots (bank = (a / 4) % 64) exactly once - conflict-free, for both halves and both values of kk % 2.
+    const int wrow = W8 ? BM * 128 + (wc * TN + (lane & 31)) * 64 + (((lane >> 5) ^ ((lane >> 2) & 3)) * 16)
+                        : (BM + wc * TN + (lane & 31)) * 128 + c0;
 
     // ---- this workgroup's work list.  Whole tiles first: round i of the data-parallel part hands tile i * P + rng to
     // workgroup rng, and workgroup b runs on XCD b % 8, so rng is XCD-contiguous: the 32 CUs of an XCD work on 32 neighbouring
@@ -183,6 +204,11 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
         const uint16_t* xb = a.X + (size_t)m0 * a.ldx + kbeg;
         const uint16_t* wb;
         int rows_w;
+        if constexpr (W8) {                           // rows of codes: ldw and kbeg count bytes
+            const uint8_t* w8 = reinterpret_cast<const uint8_t*>(a.W);
+            if constexpr (EPI == EPI_SWIGLU) { wb = reinterpret_cast<const uint16_t*>(w8 + (size_t)(tn * (BN / 2)) * a.ldw + kbeg); rows_w = BN; }
+            else { wb = reinterpret_cast<const uint16_t*>(w8 + (size_t)n0 * a.ldw + kbeg); rows_w = min(BN, a.N - n0); }
+        } else
         if constexpr (EPI == EPI_SWIGLU) { wb = a.W + (size_t)(tn * (BN / 2)) * a.ldw + kbeg; rows_w = BN; }
         else { wb = a.W + (size_t)n0 * a.ldw + kbeg; rows_w = min(BN, a.N - n0); }
         rx = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, 0x7fffffff, 0x00020000);
@@ -195,8 +221,9 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
         }
 #pragma unroll
         for (int j = 0; j < WJ; ++j) {
-            const int row = (j * NW + wave) * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((row >> 1) & 7);
+            // (codes: lane l of an image lands at byte 16 l = row l >> 2, physical chunk l & 3, and fetches the logical chunk that lives there)
+            const int row = W8 ? (j * NW + wave) * 16 + (lane >> 2) : (j * NW + wave) * 8 + (lane >> 3);
+            const int c = W8 ? (lane & 3) ^ ((row >> 2) & 3) : (lane & 7) ^ ((row >> 1) & 7);
             int src;
             if constexpr (EPI == EPI_SWIGLU) {      // tile rows: [g 0-31 | u 0-31 | g 32-63 | u 32-63 | ...] of features tn*BN/2 ..
                 const int blk = row >> 5;
@@ -204,17 +231,17 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
             } else {
                 src = min(row, rows_w - 1);
             }
-            woff[j] = (uint32_t)src * (uint32_t)(a.ldw * 2) + c * 16;
+            woff[j] = (uint32_t)src * (uint32_t)(W8 ? a.ldw : a.ldw * 2) + c * 16;
         }
     };
     auto stage = [&](int t, int buf) {
-        const int so = t * 128;
+        const int so = t * 128, sw = t * WROW;
 #pragma unroll
         for (int j = 0; j < XJ; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(lds + buf * BUF + (j * NW + wave) * 1024), 16, xoff[j], so, 0, 0);
 #pragma unroll
         for (int j = 0; j < WJ; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(lds + buf * BUF + (XIMG + j * NW + wave) * 1024), 16, woff[j], so, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(lds + buf * BUF + (XIMG + j * NW + wave) * 1024), 16, woff[j], sw, 0, 0);
     };
 
     auto stage_x = [&](int t, int buf) {
@@ -224,7 +251,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(lds + buf * BUF + (j * NW + wave) * 1024), 16, xoff[j], so, 0, 0);
     };
     auto stage_w = [&](int t, int buf) {
-        const int so = t * 128;
+        const int so = t * WROW;
 #pragma unroll
         for (int j = 0; j < WJ; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(lds + buf * BUF + (XIMG + j * NW + wave) * 1024), 16, woff[j], so, 0, 0);
@@ -272,9 +299,25 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
             }
         };
         frag8_t xg[4][MI], wg[4][NI];
+        [[maybe_unused]] uint2 wq[2][NI];       // 8-bit weight form: the codes of k-steps 2 and 3, read together with those of k-steps 0 and 1
         auto rd = [&](int buf, int kk) {
+            if constexpr (W8) {
+                // one 16-byte read per lane at k-steps 0 and 1 yields the codes of two k-steps; those of kk + 2 wait in wq until the
+                // set wg[kk + 2] is free (where the 16-bit form issues its read) and are widened there: no LDS read of W at k-steps 2 and 3
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    if (kk < 2) {
+                        const uint4 c = *reinterpret_cast<const uint4*>(lds + buf * BUF + ((wrow + i * 2048) ^ (kk << 5)));
+                        wg[kk][i] = __builtin_bit_cast(frag8_t, w8_widen(make_uint2(c.x, c.y)));
+                        wq[kk & 1][i] = make_uint2(c.z, c.w);
+                    } else {
+                        wg[kk][i] = __builtin_bit_cast(frag8_t, w8_widen(wq[kk & 1][i]));
+                    }
+                }
+            } else {
 #pragma unroll
             for (int i = 0; i < NI; ++i) wg[kk][i] = *reinterpret_cast<const frag8_t*>(lds + buf * BUF + ((wrow + i * 4096) ^ (kk << 5)));
+            }
 #pragma unroll
             for (int i = 0; i < MI; ++i) xg[kk][i] = *reinterpret_cast<const frag8_t*>(lds + buf * BUF + ((xrow + i * 4096) ^ (kk << 5)));
         };
@@ -406,8 +449,30 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
         more = advance();
         if (more) { setup(); stage_first(); }
 
+        // ---- 8-bit weight form: the row scale of W, a power of two, goes onto the fp32 sums of its output column - behind the stream-K
+        // fix-up (the partials travel unscaled: only the finisher multiplies, and a power of two commutes with the additions, so the bits
+        // are those of scaled partials), before bias and the first rounding; for SwiGLU gate and up take their own rows of w_scale [2 F];
+        // for slabs before the slab store.
+        [[maybe_unused]] auto scale_acc = [&]() {
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int col = wc * TN + i * 32 + q * 8 + 4 * (lane >> 5);       // column of the tile = row of its W image
+                    int sn;
+                    if constexpr (EPI == EPI_SWIGLU) { const int blk = col >> 5; sn = (blk & 1) * a.N + ctn * (BN / 2) + (blk >> 1) * 32 + (col & 31); }
+                    else sn = cn0 + col;
+                    f32x4_t sc = {1.f, 1.f, 1.f, 1.f};
+                    if (EPI == EPI_SWIGLU || sn < a.N) sc = *reinterpret_cast<const f32x4_t*>(a.w_scale + sn);
+#pragma unroll
+                    for (int j = 0; j < MI; ++j)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) acc[i][j][q * 4 + e] *= sc[e];
+                }
+        };
         // ---- split-K slab mode: the partial product of this (tile, K part) goes to its slab as it is; the consumer adds the slabs
         if constexpr (SLAB) {
+            if constexpr (W8) scale_acc();
             float* sl = a.slabs + (size_t)cpart * a.M * a.N;
 #pragma unroll
             for (int i = 0; i < NI; ++i)
@@ -505,6 +570,8 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
                 }
             }
         }
+
+        if constexpr (W8) scale_acc();
 
         // ---- epilogue.  acc[i][j][e]: n = wc*TN + i*32 + (e&3) + 8*(e>>2) + 4*(lane>>5),  m = wr*TM + j*32 + (lane&31)
         const int mrow = cm0 + wr * TM + (lane & 31);
@@ -647,7 +714,7 @@ int num_workgroups() {
     return g_num_cu;
 }
 
-template <int BM, int BN, int WM, int WN>
+template <int BM, int BN, int WM, int WN, bool W8 = false>
 int launch_cfg(const GemmArgs& a0, int epi, int sched, void* workspace, int64_t workspace_bytes, hipStream_t st) {
     GemmArgs a = a0;
     const int ncols = epi == EPI_SWIGLU ? 2 * a.N : a.N;
@@ -681,18 +748,39 @@ int launch_cfg(const GemmArgs& a0, int epi, int sched, void* workspace, int64_t 
     a.counter = (int*)workspace;
     a.partial = (float*)((char*)workspace + COUNTER_BYTES);
     const dim3 grid(P), block(WM * WN * 64);
-    const size_t smem = (size_t)gemm_stages(BM, BN, WM, WN) * (BM + BN) * 128 + gemm_staging_bytes(BN, WM, WN);      // + the epilogue's staging blocks
-    static_assert(gemm_stages(BM, BN, WM, WN) * (BM + BN) * 128 + gemm_staging_bytes(BN, WM, WN) <= LDS_BYTES, "LDS");
-    static_assert((gemm_stages(BM, BN, WM, WN) - 1) * ((BM + BN) / 8 / (WM * WN)) <= 63, "vmcnt is 6 bits");
+    constexpr int NSTG = W8 ? gemm_stages_w8(BM, BN, WM, WN) : gemm_stages(BM, BN, WM, WN);
+    constexpr int BUF = BM * 128 + BN * (W8 ? 64 : 128), NLD = (BM / 8 + (W8 ? BN / 16 : BN / 8)) / (WM * WN);
+    const size_t smem = (size_t)NSTG * BUF + gemm_staging_bytes(BN, WM, WN);      // + the epilogue's staging blocks
+    static_assert(NSTG * BUF + gemm_staging_bytes(BN, WM, WN) <= LDS_BYTES, "LDS");
+    static_assert((NSTG - 1) * NLD <= 63, "vmcnt is 6 bits");
     a.stage_out = ((a.ldy % 8) == 0 && (((uintptr_t)a.Y) & 15) == 0) ? 1 : 0;
 #define VDD_GEMM_LAUNCH(E)                                                                                            \
     case E: {                                                                                                         \
-        auto kfn = gemm_kernel<BM, BN, WM, WN, E>;                                                                       \
+        auto kfn = gemm_kernel<BM, BN, WM, WN, E, W8>;                                                                     \
         static bool attr_set = false;                                                                                 \
         if (!attr_set) { (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); attr_set = true; } \
         hipLaunchKernelGGL(kfn, grid, block, smem, st, a);                                                            \
         break;                                                                                                        \
     }
+    if constexpr (W8) {
+        // the 8-bit weight form: W-stream tiles only (three or more K-tile buffers), epilogues NONE / BIAS / SWIGLU and the slabs of the 64 x 256 tile
+        if constexpr (gemm_stages(BM, BN, WM, WN) >= 3 && (BN / 16) % (WM * WN) == 0) {
+            if (a.slab_S > 0) {
+                if constexpr (BM == 64 && BN == 256) { epi = EPI_SLABS; switch (epi) { VDD_GEMM_LAUNCH(EPI_SLABS) } }
+                else return VDD_ERR_UNSUPPORTED;
+            } else switch (epi) {
+                VDD_GEMM_LAUNCH(EPI_NONE)
+                VDD_GEMM_LAUNCH(EPI_BIAS)
+                case EPI_SWIGLU:
+                    if constexpr ((BN / WN / 32) % 2 == 0 && 256 % BN == 0) { switch (epi) { VDD_GEMM_LAUNCH(EPI_SWIGLU) } break; }
+                    else return VDD_ERR_UNSUPPORTED;
+                default: return VDD_ERR_UNSUPPORTED;
+            }
+            return hipGetLastError() == hipSuccess ? VDD_OK : VDD_ERR_LAUNCH;
+        } else {
+            return VDD_ERR_UNSUPPORTED;
+        }
+    } else {
     if (a.slab_S > 0) {
         if constexpr (BM == 64) { epi = EPI_SLABS; switch (epi) { VDD_GEMM_LAUNCH(EPI_SLABS) } return hipGetLastError() == hipSuccess ? VDD_OK : VDD_ERR_LAUNCH; }
         else return VDD_ERR_INVALID_ARG;           // split-K slabs: the 64 x 256 tile (config 8) only
@@ -712,8 +800,43 @@ int launch_cfg(const GemmArgs& a0, int epi, int sched, void* workspace, int64_t 
             }
         default: return VDD_ERR_INVALID_ARG;
     }
-#undef VDD_GEMM_LAUNCH
     return hipGetLastError() == hipSuccess ? VDD_OK : VDD_ERR_LAUNCH;
+    }
+#undef VDD_GEMM_LAUNCH
+}
+
+// the macro tile ids of vdd_gemm / vdd_gemm_w8 (config bits 0-3 + 6-7); W8: the 8-bit weight form (launch_cfg refuses the tiles it does not serve)
+template <bool W8>
+int dispatch_cfg(int config, const GemmArgs& a, int epilogue, int sched, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+    switch (config) {
+        case 1: return launch_cfg<256, 256, 2, 4, W8>(a, epilogue, sched, workspace, workspace_bytes, st);
+        case 2: return launch_cfg<128, 256, 2, 4, W8>(a, epilogue, sched, workspace, workspace_bytes, st);
+        case 3: return launch_cfg<256, 128, 4, 2, W8>(a, epilogue, sched, workspace, workspace_bytes, st);
+        case 4: return launch_cfg<192, 256, 2, 4, W8>(a, epilogue, sched, workspace, workspace_bytes, st);
+        case 5: return launch_cfg<256, 192, 4, 2, W8>(a, epilogue, sched, workspace, workspace_bytes, st);
+        case 6: return launch_cfg<192, 192, 2, 3, W8>(a, epilogue, sched, workspace, workspace_bytes, st);      // 6 waves of 96 x 64
+        case 7: return launch_cfg<192, 128, 2, 4, W8>(a, epilogue, sched, workspace, workspace_bytes, st);      // 8 waves of 96 x 32
+        case 8: return launch_cfg<64, 256, 2, 4, W8>(a, epilogue, sched, workspace, workspace_bytes, st);       // a few dozen rows: W streaming,
+                                                                                                            // 64-KiB partial slabs
+        // W streams for 65 - 256 rows (gemm_stages: 4 - 5 K-tile buffers); 10 / 11 pair gate / up inside a wave (SwiGLU epilogue)
+        case 9: return launch_cfg<128, 128, 2, 4, W8>(a, epilogue, sched, workspace, workspace_bytes, st);      // 8 waves of 64 x 32
+        case 10: return launch_cfg<128, 128, 2, 2, W8>(a, epilogue, sched, workspace, workspace_bytes, st);     // 4 waves of 64 x 64
+        case 11: return launch_cfg<192, 128, 2, 2, W8>(a, epilogue, sched, workspace, workspace_bytes, st);     // 4 waves of 96 x 64
+        // up to 64 rows (round 6): the row tile is the batch, six K-tile buffers; 12 pairs gate / up inside a wave
+        case 12: return launch_cfg<64, 128, 2, 2, W8>(a, epilogue, sched, workspace, workspace_bytes, st);      // 4 waves of 32 x 64
+        case 13: return launch_cfg<64, 128, 2, 4, W8>(a, epilogue, sched, workspace, workspace_bytes, st);      // 8 waves of 32 x 32
+        case 14: return launch_cfg<32, 128, 1, 4, W8>(a, epilogue, sched, workspace, workspace_bytes, st);      // up to 32 rows: 4 waves of 32 x 32, eight buffers
+        case 15: return launch_cfg<32, 128, 1, 2, W8>(a, epilogue, sched, workspace, workspace_bytes, st);      // 2 waves of 32 x 64 (gate / up pairs)
+        // a 96-row tile: a batch of 270 rows (90 questions x 3 branches, BASELINE config #3) is three of them (288 rows) where 128- / 192-row tiles compute
+        // 384.  Measured (tools/gemm_96_tile_ab.py): the tuner takes it for the d x d attention-output projection at 90 - 360 rows (13B step at 270 rows
+        // 22.8 -> 22.0 ms) and for nothing else - the wide projections keep their 192-row tiles, whose padding costs less than streaming W a third
+        // time; the 2-wave and 96 x 256 variants of it were never picked and are not built
+        case 16: return launch_cfg<96, 128, 1, 4, W8>(a, epilogue, sched, workspace, workspace_bytes, st);      // 4 waves of 96 x 32, five buffers
+        // (launch_cfg<256, 256, 2, 2> - four waves of 128 x 128, one per SIMD with 512 registers, the vendor kernel's shape - instantiates as it
+        //  is and was measured: 1.10 PF/s on random data, 1.27 on zero operands against 1.27 / 1.6 for the 8-wave tile: a lone wave per SIMD
+        //  stalls its own MFMAs behind every LDS-DMA issue and fragment read.  profiles/r04_gemm_data_dependence.jsonl)
+        default: return W8 ? VDD_ERR_UNSUPPORTED : VDD_ERR_INVALID_ARG;
+    }
 }
 
 }  // namespace VDD_ELEM_NS
@@ -753,35 +876,35 @@ VDD_HIDDEN int VDD_IMPL(vdd_gemm)(const void* X, const void* W, void* Y, const v
     }
     config = (config & 15) | (((config >> 6) & 3) << 4);      // macro tile id: bits 0-3 + bits 6-7 (ids 16 ..: round 6)
     if (config == 0) config = 1;
-    switch (config) {
-        case 1: return launch_cfg<256, 256, 2, 4>(a, epilogue, sched, workspace, workspace_bytes, st);
-        case 2: return launch_cfg<128, 256, 2, 4>(a, epilogue, sched, workspace, workspace_bytes, st);
-        case 3: return launch_cfg<256, 128, 4, 2>(a, epilogue, sched, workspace, workspace_bytes, st);
-        case 4: return launch_cfg<192, 256, 2, 4>(a, epilogue, sched, workspace, workspace_bytes, st);
-        case 5: return launch_cfg<256, 192, 4, 2>(a, epilogue, sched, workspace, workspace_bytes, st);
-        case 6: return launch_cfg<192, 192, 2, 3>(a, epilogue, sched, workspace, workspace_bytes, st);      // 6 waves of 96 x 64
-        case 7: return launch_cfg<192, 128, 2, 4>(a, epilogue, sched, workspace, workspace_bytes, st);      // 8 waves of 96 x 32
-        case 8: return launch_cfg<64, 256, 2, 4>(a, epilogue, sched, workspace, workspace_bytes, st);       // a few dozen rows: W streaming,
-                                                                                                            // 64-KiB partial slabs
-        // W streams for 65 - 256 rows (gemm_stages: 4 - 5 K-tile buffers); 10 / 11 pair gate / up inside a wave (SwiGLU epilogue)
-        case 9: return launch_cfg<128, 128, 2, 4>(a, epilogue, sched, workspace, workspace_bytes, st);      // 8 waves of 64 x 32
-        case 10: return launch_cfg<128, 128, 2, 2>(a, epilogue, sched, workspace, workspace_bytes, st);     // 4 waves of 64 x 64
-        case 11: return launch_cfg<192, 128, 2, 2>(a, epilogue, sched, workspace, workspace_bytes, st);     // 4 waves of 96 x 64
-        // up to 64 rows (round 6): the row tile is the batch, six K-tile buffers; 12 pairs gate / up inside a wave
-        case 12: return launch_cfg<64, 128, 2, 2>(a, epilogue, sched, workspace, workspace_bytes, st);      // 4 waves of 32 x 64
-        case 13: return launch_cfg<64, 128, 2, 4>(a, epilogue, sched, workspace, workspace_bytes, st);      // 8 waves of 32 x 32
-        case 14: return launch_cfg<32, 128, 1, 4>(a, epilogue, sched, workspace, workspace_bytes, st);      // up to 32 rows: 4 waves of 32 x 32, eight buffers
-        case 15: return launch_cfg<32, 128, 1, 2>(a, epilogue, sched, workspace, workspace_bytes, st);      // 2 waves of 32 x 64 (gate / up pairs)
-        // a 96-row tile: a batch of 270 rows (90 questions x 3 branches, BASELINE config #3) is three of them (288 rows) where 128- / 192-row tiles compute
-        // 384.  Measured (tools/gemm_96_tile_ab.py): the tuner takes it for the d x d attention-output projection at 90 - 360 rows (13B step at 270 rows
-        // 22.8 -> 22.0 ms) and for nothing else - the wide projections keep their 192-row tiles, whose padding costs less than streaming W a third
-        // time; the 2-wave and 96 x 256 variants of it were never picked and are not built
-        case 16: return launch_cfg<96, 128, 1, 4>(a, epilogue, sched, workspace, workspace_bytes, st);      // 4 waves of 96 x 32, five buffers
-        // (launch_cfg<256, 256, 2, 2> - four waves of 128 x 128, one per SIMD with 512 registers, the vendor kernel's shape - instantiates as it
-        //  is and was measured: 1.10 PF/s on random data, 1.27 on zero operands against 1.27 / 1.6 for the 8-wave tile: a lone wave per SIMD
-        //  stalls its own MFMAs behind every LDS-DMA issue and fragment read.  profiles/r04_gemm_data_dependence.jsonl)
-        default: return VDD_ERR_INVALID_ARG;
+    return dispatch_cfg<false>(config, a, epilogue, sched, workspace, workspace_bytes, st);
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_gemm_w8)(const void* X, const void* W8, const float* w_scale, void* Y, const void* bias, int M, int N, int K, int64_t ldx,
+             int64_t ldy, int epilogue, int config, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (M <= 0 || N <= 0) return VDD_OK;
+    if (!X || !W8 || !w_scale || !Y || K <= 0 || (ldx % 8) || (ldy % 4) || N % 4 != 0 || ((uintptr_t)w_scale & 15)) return VDD_ERR_INVALID_ARG;
+    // what this entry does not serve, before anything is launched: the caller runs vdd_gemm on w16
+    if (K % 128 != 0) return VDD_ERR_UNSUPPORTED;
+    if (epilogue != EPI_NONE && epilogue != EPI_BIAS && epilogue != EPI_SWIGLU) return VDD_ERR_UNSUPPORTED;
+    if (epilogue == EPI_BIAS && !bias) return VDD_ERR_INVALID_ARG;
+    if (epilogue == EPI_SWIGLU && N % 128 != 0) return VDD_ERR_INVALID_ARG;
+    // per-lane byte offsets inside a tile are 32-bit: 256 rows of X, and for SwiGLU the gate -> up distance in the codes (K bytes a row)
+    if ((uint64_t)256 * (uint64_t)ldx * 2 >= 0x7fffffffull) return VDD_ERR_INVALID_ARG;
+    if ((uint64_t)((epilogue == EPI_SWIGLU ? (uint64_t)N : 0) + 256) * (uint64_t)K >= 0x7fffffffull) return VDD_ERR_UNSUPPORTED;
+    GemmArgs a{};
+    a.X = (const uint16_t*)X; a.W = (const uint16_t*)W8; a.w_scale = w_scale; a.Y = (uint16_t*)Y;
+    a.bias = (const uint16_t*)bias;
+    a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = K; a.ldy = ldy;
+    hipStream_t st = (hipStream_t)stream;
+    const int sched = (config >> 4) & 3;
+    if (sched == 3) {
+        a.slab_S = (config >> 8) & 255;
+        a.slabs = (float*)Y;
+        if (a.slab_S < 1 || epilogue != EPI_NONE || ldy != N || ((uintptr_t)Y & 15)) return VDD_ERR_INVALID_ARG;
     }
+    config = (config & 15) | (((config >> 6) & 3) << 4);
+    if (config == 0) config = 1;
+    return dispatch_cfg<true>(config, a, epilogue, sched, workspace, workspace_bytes, st);
 }
 
 }  // extern "C"

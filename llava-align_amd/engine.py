@@ -522,10 +522,11 @@ class LanguageModel:
             padded[:V] = self.lm_head
             self.lm_head = padded
 
-    def _head(self, a=None, resid=None, ss=None):
-        """Final norm (fused for a few rows) + output projection -> [rows, V] logits."""
+    def _head(self, a=None, resid=None, ss=None, codes=False):
+        """Final norm (fused for a few rows) + output projection -> [rows, V] logits.  codes: a decode step's head - lm_head goes to
+        ops.linear with its 8-bit codes (the prefill's head, `logits`, reads w16 as ever)."""
         c = self.cfg
-        y = ops.linear(a, self.lm_head) if a is not None else ops.linear_normed(resid, ss, self.w.t["norm"], c.eps, self.lm_head,
+        y = ops.linear(a, self.lm_head, w8=self.w.w8("lm_head") if codes else None) if a is not None else ops.linear_normed(resid, ss, self.w.t["norm"], c.eps, self.lm_head,
                                                                                 w8=self.w.w8("lm_head"))
         return y if y.shape[1] == c.vocab else y[:, :c.vocab]
 
@@ -651,8 +652,10 @@ class LanguageModel:
 
     @torch.no_grad()
     def _decode_layers(self, resid, pos, cpos, slot, attn_rows, kv, grouping, workspace):
-        """The decoder layers + head of a decode step with stand-alone RMSNorm launches (seven launches per layer at a few rows)."""
-        c, t = self.cfg, self.w.t
+        """The decoder layers + head of a decode step with stand-alone RMSNorm launches (seven launches per layer at a few rows).  Weights
+        quantised by LlavaWeights.quantize_lm_w8 go to the projections with their codes: up to ops.W8_GEMM_MAX_M rows the MFMA GEMM's
+        W-stream tiles read those where that was measured faster (the same bits as on the dequantised weight)."""
+        c, t, w8 = self.cfg, self.w.t, self.w.w8
         H, Hkv, D = c.n_heads, c.n_kv_heads, c.head_dim
         M = resid.shape[0]
         delta = None
@@ -662,7 +665,7 @@ class LanguageModel:
                 a = ops.rmsnorm(resid, t[p + "ln1"], c.eps)
             else:
                 a = ops.rmsnorm(resid, t[p + "ln1"], c.eps, delta=delta, resid_out=resid)
-            qkv = ops.linear(a, t[p + "wqkv"], bias=t[p + "bqkv_lm"] if c.qkv_bias else None)
+            qkv = ops.linear(a, t[p + "wqkv"], bias=t[p + "bqkv_lm"] if c.qkv_bias else None, w8=w8(p + "wqkv"))
             if kv.n_pages:
                 q = ops.rope_kv_write_paged(qkv, pos, slot, self.cs, kv.pk[i], kv.pv[i], kv.page_table, H, Hkv, D, cpos=cpos)
                 att = ops.decode_attention_paged(q, kv.pk[i], kv.pv[i], kv.page_table, attn_rows, H, Hkv, D, kv.kp[i], kv.vp[i],
@@ -681,11 +684,11 @@ class LanguageModel:
                 q = ops.rope_kv_write(qkv, pos, slot, self.cs, kv.ko[i], kv.vo[i], H, Hkv, D, cpos=cpos)
                 att = ops.decode_attention(q, kv.ko[i], kv.vo[i], attn_rows, H, Hkv, D, k_prefix=kv.kp[i], v_prefix=kv.vp[i],
                                            max_len=kv.t_pre + kv.t_own, workspace=workspace)
-            o = ops.linear_to_norm(att, t[p + "wo"])
+            o = ops.linear_to_norm(att, t[p + "wo"], w8=w8(p + "wo"))
             a = ops.rmsnorm(resid, t[p + "ln2"], c.eps, delta=o, resid_out=resid)
-            delta = ops.linear_to_norm(ops.swiglu_linear(a, t[p + "wgu"]), t[p + "wd"])
+            delta = ops.linear_to_norm(ops.swiglu_linear(a, t[p + "wgu"], w8=w8(p + "wgu")), t[p + "wd"], w8=w8(p + "wd"))
         a = ops.rmsnorm(resid, t["norm"], c.eps, delta=delta)
-        return self._head(a)
+        return self._head(a, codes=True)
 
 
 # ------------------------------------------------------------------ generation

@@ -42,6 +42,7 @@ _SIGS = {
     "vdd_skinny_gemm_resid_ss_w8": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _P],
     "vdd_skinny_gemm_normed_w8": [_P, _P, _I, _P, _F, _P, _P, _P, _I, _I, _I, _L, _L, _I, _P],
     "vdd_skinny_swiglu_normed_w8": [_P, _P, _I, _P, _F, _P, _P, _P, _I, _I, _I, _L, _I, _P],
+    "vdd_gemm_w8": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _I, _I, _P, _L, _I, _P],
     "vdd_rope_kv_write_paged": [_P] * 9 + [_I, _I, _I, _I, _L, _I, _I, _I, _I, _P],
     "vdd_decode_attention_paged": [_P] * 9 + [_I, _I, _I, _I, _L, _I, _I, _I, _L, _I, _I, _F, _I, _P],
     "vdd_kv_pages_scatter": [_P] * 7 + [_I, _I, _I, _I, _L, _I, _L, _I, _I, _I, _I, _P],
@@ -202,9 +203,10 @@ SLAB_NORM_MAX_M = 256   # rows up to which a d-wide projection that would take t
                         # 64 x 256 tiles alone fill a quarter of the chip and slab_splits() returns 0)
 
 
-def gemm_slabs(x, w, n_split, out=None, tile=8):
+def gemm_slabs(x, w, n_split, out=None, tile=8, w8=None):
     """fp32 [n_split, M, N] partial products of x @ w^T (split-K over n_split parts of K, one (tile, part) per workgroup, no fix-up):
-    for a consumer that adds them - rmsnorm(delta=slabs)."""
+    for a consumer that adds them - rmsnorm(delta=slabs).  w8: (codes, scale) of w (quantize_w8) - streamed instead where vdd_gemm_w8
+    serves the call (the same bits)."""
     dt = _dt(x, w)
     M, K = x.shape
     N = w.shape[0]
@@ -212,6 +214,11 @@ def gemm_slabs(x, w, n_split, out=None, tile=8):
         raise ValueError(f"gemm_slabs: K % 128, N % 4, 1 <= n_split <= K / 128 (got M={M} N={N} K={K} n_split={n_split})")
     out = torch.empty(n_split, M, N, dtype=torch.float32, device=x.device) if out is None else out
     ws = _gemm_workspace(x.device, M, N)
+    q = _w8_args(w, w8)
+    if q is not None and _w8_done(_lib_ready().vdd_gemm_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), None, M, N, K,
+                                                            x.stride(0), N, EPI_NONE, tile + 16 * 3 + (n_split << 8), ws.data_ptr(),
+                                                            ws.numel(), dt, _st(x))):
+        return out
     _lib.check(_lib_ready().vdd_gemm(x.data_ptr(), w.data_ptr(), out.data_ptr(), None, None, M, N, K, x.stride(0), w.stride(0), N, 0,
                                      EPI_NONE, tile + 16 * 3 + (n_split << 8), ws.data_ptr(), ws.numel(), dt, _st(x)))
     return out
@@ -225,7 +232,7 @@ def slab_splits(M, N, K, n_cu=256):
     return s if s >= 4 else 0
 
 
-def linear_to_norm(x, w):
+def linear_to_norm(x, w, w8=None):
     """Projection whose only consumer is the next RMSNorm's residual add (attention output / MLP down projection): returns either
     the [M, N] product (weight-streaming kernel or MFMA GEMM) or fp32 split-K slabs [S, M, N] that rmsnorm(delta=...) adds, rounds and
     then adds to the residual stream - the same roundings as a rounded product followed by the add.  Which of the three is MEASURED once
@@ -233,7 +240,8 @@ def linear_to_norm(x, w):
     DESIGN_APPENDIX): N = d gives the GEMM 16 - 32 output tiles at a few dozen rows - as a finished product each is cut over 8 - 16
     workgroups and put together by ONE that reads the others' partial tiles in turn, as slabs nobody waits; the weight-streaming kernel
     re-reads X per column block and, when N / 16 column blocks do not divide over the CUs (d = 5120: 320 blocks on 256), runs a second
-    round for a quarter of the chip."""
+    round for a quarter of the chip.
+    w8: (codes, scale) of w - the GEMM and the slabs on codes ("gemm8", "slabs8") join the measurement, under a kind of its own."""
     M, K = x.shape
     N = w.shape[0]
     cands = {}
@@ -244,16 +252,22 @@ def linear_to_norm(x, w):
     s_ = slab_splits(M, N, K) if (M <= 256 and N <= 8192 and K % 256 == 0) else 0
     if s_:
         cands["slabs"] = lambda wi: gemm_slabs(x, wi, s_)
-    form = _pick_form("to_norm", M, N, K, x, w, cands, consumer="norm")
-    if form == "slabs":
-        return gemm_slabs(x, w, s_)
-    return skinny_gemm(x, w) if form == "skinny" else gemm(x, w)
+    q = _w8_form_args(w, w8, M, K, N)
+    if q is not None:
+        cands["gemm8"] = lambda wi, qi: gemm(x, wi, w8=qi)
+        if s_:
+            cands["slabs8"] = lambda wi, qi: gemm_slabs(x, wi, s_, w8=qi)
+    form = _pick_form("to_norm8" if q is not None else "to_norm", M, N, K, x, w, cands, consumer="norm", w8=q)
+    if form in ("slabs", "slabs8"):
+        return gemm_slabs(x, w, s_, w8=q if form == "slabs8" else None)
+    return skinny_gemm(x, w) if form == "skinny" else gemm(x, w, w8=q if form == "gemm8" else None)
 
 
 NORM_FUSED_MAX_M = 16   # rows up to which the normalise-once projections EXIST (their LDS image of the normalised rows; see norm_fused_rows)
 
 
-FORCE_FORM = {}             # tests / probes: kind ("linear", "to_norm", "swiglu") -> "skinny" | "gemm" | "slabs" wins whenever it is eligible
+FORCE_FORM = {}             # tests / probes: kind ("linear", "to_norm", "swiglu"; "linear8", "to_norm8", "swiglu8" with codes) -> "skinny" | "gemm" |
+                            # "slabs" | "gemm8" | "slabs8" wins whenever it is eligible
 FORCE_LAYER_FORM = None     # tests / probes: "fused" | "plain" for every row count the fused layer serves
 
 
@@ -391,6 +405,23 @@ def _w8_args(w, w8):
             or not codes.is_contiguous() or not scale.is_contiguous() or codes.device != w.device:
         raise ValueError("w8 = (uint8 codes [N, K] from quantize_w8, fp32 scale [N]) of the same weight")
     return codes, scale
+
+
+# The W-stream tiles of the MFMA GEMM read codes too (vdd_gemm_w8, 17 - 256 rows and the plain layer at any row count up to 256): the tile ids
+# with three or more K-tile buffers.  Which of them and which schedule is tuned under keys of its own (`_gemm_key_w8`), and whether a
+# projection takes the GEMM on codes at all is measured by `_pick_form` under kinds of its own ("linear8", "to_norm8", "swiglu8"): the
+# 16-bit tables are neither read for nor overwritten by an 8-bit model.
+W8_GEMM_TILES = (7, 8, 9, 10, 11, 12, 13, 14, 15, 16)
+W8_GEMM_MAX_M = 256
+
+
+def _w8_form_args(w, w8, M, K, N):
+    """(codes, scale) if the 8-bit GEMM forms are candidates for this projection: codes given, the switch on, not the batch-invariant mode
+    (one form per op there), M <= W8_GEMM_MAX_M and a shape the GEMM takes."""
+    q = _w8_args(w, w8)
+    if q is None or GEMM_BATCH_INVARIANT or M > W8_GEMM_MAX_M or K % 128 != 0 or N % 4 != 0:
+        return None
+    return q
 
 
 def _w8_done(rc) -> bool:
@@ -532,10 +563,11 @@ def _pick_timed(key, thunks, device, n_rot, iters=8):
     return got
 
 
-def _pick_form(kind, M, N, K, x, w, cands, consumer=None):
+def _pick_form(kind, M, N, K, x, w, cands, consumer=None, w8=None):
     """Which of `cands` (name -> fn(weight)) runs this [M, K] x [N, K]^T product.  One eligible form: that one.  Batch-invariant mode: the
     GEMM.  Else the measured one; a product whose consumer is the next RMSNorm is timed WITH that norm (slabs make the norm add S fp32
-    partials: cheaper projection, dearer norm)."""
+    partials: cheaper projection, dearer norm).  w8 = (codes, scale): the candidates whose name ends in "8" are fn(weight, (codes, scale))
+    and are timed on rotating copies of the codes."""
     if GEMM_BATCH_INVARIANT and "gemm" in cands:
         return "gemm"
     if len(cands) == 1:
@@ -555,11 +587,19 @@ def _pick_form(kind, M, N, K, x, w, cands, consumer=None):
         copies = [w] + [w.clone() for _ in range(n_copies - 1)]
     except torch.OutOfMemoryError:
         copies = [w]
+    if w8 is not None:
+        try:
+            qcopies = [w8] + [(w8[0].clone(), w8[1]) for _ in range(len(copies) - 1)]
+        except torch.OutOfMemoryError:
+            qcopies = [w8]
+        run = {n_: ((lambda i, f=f: f(copies[i], qcopies[i % len(qcopies)])) if n_.endswith("8") else (lambda i, f=f: f(copies[i]))) for n_, f in cands.items()}
+    else:
+        run = {n_: (lambda i, f=f: f(copies[i])) for n_, f in cands.items()}
     if consumer == "norm":
         res, lnw = torch.zeros(M, N, dtype=x.dtype, device=x.device), torch.ones(N, dtype=x.dtype, device=x.device)
-        thunks = {n_: (lambda i, f=f: rmsnorm(res, lnw, 1e-5, delta=f(copies[i]))) for n_, f in cands.items()}
+        thunks = {n_: (lambda i, f=f: rmsnorm(res, lnw, 1e-5, delta=f(i))) for n_, f in run.items()}
     else:
-        thunks = {n_: (lambda i, f=f: f(copies[i])) for n_, f in cands.items()}
+        thunks = run
     got = _pick_timed(key, thunks, x.device, len(copies))
     return got if got is not None else fallback
 
@@ -637,6 +677,12 @@ def gemm_workspace_reset(device=None):
             ws[: 4 << 20].zero_()
 
 
+def _gemm_w8_call(x, q, out, bias, M, N, K, epi, config, ws) -> bool:
+    """vdd_gemm_w8 on q = (codes, scale): True = launched (and counted), False = not served (nothing launched, `out` untouched)."""
+    return _w8_done(_lib_ready().vdd_gemm_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                             M, N, K, x.stride(0), out.stride(0), epi, config, ws.data_ptr(), ws.numel(), _MODEL_DT[x.dtype], _st(x)))
+
+
 def _gemm_call(x, w, out, bias, resid, M, N, K, epi, config, ws):
     dt = _MODEL_DT[x.dtype]                                   # (gemm() has checked the operands)
     _lib.check(_lib_ready().vdd_gemm(x.data_ptr(), w.data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else None,
@@ -644,9 +690,13 @@ def _gemm_call(x, w, out, bias, resid, M, N, K, epi, config, ws):
                                      resid.stride(0) if resid is not None else 0, epi, config, ws.data_ptr(), ws.numel(), dt, _st(x)))
 
 
-def gemm(x, w, bias=None, resid=None, epi=EPI_NONE, out=None, config=None):
+def gemm(x, w, bias=None, resid=None, epi=EPI_NONE, out=None, config=None, w8=None):
     """out[M, N] = epilogue(x[M, K] @ w[N, K]^T) on the hand-written MFMA kernel (bf16 or fp16 operands, fp32 accumulate).  epi=EPI_SWIGLU:
-    w = [Wgate; Wup], N = w.shape[0] // 2.  No library fallback: unsupported shapes raise."""
+    w = [Wgate; Wup], N = w.shape[0] // 2.  No library fallback: unsupported shapes raise.
+    w8: (codes, scale) of w (quantize_w8).  With ops.W8_DECODE on and a `config` vdd_gemm_w8 serves, the codes are streamed instead of w -
+    the same bits (include/vdd_hip.h); config=None: tile and schedule tuned among the W-stream tiles under a key of its own; anything the
+    8-bit entry does not serve runs as ever on w."""
+    q = _w8_args(w, w8)
     dt = _dt(x, w, bias, resid)
     M, K = x.shape
     N = w.shape[0] // 2 if epi == EPI_SWIGLU else w.shape[0]
@@ -656,6 +706,10 @@ def gemm(x, w, bias=None, resid=None, epi=EPI_NONE, out=None, config=None):
     if M == 0:
         return out
     ws = _gemm_workspace(x.device, M, N)
+    if q is not None and resid is None and epi in (EPI_NONE, EPI_BIAS, EPI_SWIGLU):
+        cfg8 = config if config is not None else (_gemm_w8_config(x, q, out, bias, M, N, K, epi, dt, ws) if M <= W8_GEMM_MAX_M else None)
+        if cfg8 is not None and _gemm_w8_call(x, q, out, bias, M, N, K, epi, cfg8, ws):
+            return out
     if config is None:
         key = _gemm_key(M, N, K, epi, dt)
         config = _gemm_choice.get(key)
@@ -677,6 +731,34 @@ def gemm(x, w, bias=None, resid=None, epi=EPI_NONE, out=None, config=None):
                 _gemm_choice[key] = config
     _gemm_call(x, w, out, bias, resid, M, N, K, epi, config, ws)
     return out
+
+
+def _gemm_key_w8(M, N, K, epi, dt):
+    """Tuning key of the GEMM on codes: the 16-bit key's buckets with 8 added to the storage type (the last slot: 9 fp16, 10 bf16) - no 16-bit
+    entry, persisted or in the process, has such a key, and the cache file's "b,N,K,epi,inv,dt" form carries it as it is."""
+    return _gemm_key(M, N, K, epi, dt + 8)
+
+
+def _gemm_w8_config(x, q, out, bias, M, N, K, epi, dt, ws):
+    """Tile / schedule of the GEMM on codes for this shape: the process table, the cache file, or a timing run now; None where it cannot be
+    measured here (the tuner off, a capture in progress) or no W-stream tile serves the call - the caller runs the 16-bit GEMM."""
+    if GEMM_BATCH_INVARIANT:
+        return None
+    key = _gemm_key_w8(M, N, K, epi, dt)
+    config = _gemm_choice.get(key)
+    if config is None and GEMM_AUTOTUNE:
+        _load_persisted(x.device)
+        config = _gemm_choice.get(key)
+        if config is None and not torch.cuda.is_current_stream_capturing():
+            with _CacheLock():
+                _read_cache_section()
+                config = _gemm_choice.get(key)
+                if config is None:
+                    config = _gemm_tune(x, None, out, bias, None, M, N, K, epi, ws, w8=q)
+                    if config is not None:
+                        _gemm_choice[key] = config
+                        _store_persisted(key, config)
+    return config
 
 
 GEMM_AUTOTUNE = True            # False: 256 x 256 tiles + the hybrid schedule for every shape (no timing runs at all)
@@ -877,17 +959,29 @@ def _store_persisted(key, cfg):
         pass
 
 
-def _gemm_tune(x, w, out, bias, resid, M, N, K, epi, ws, iters=8):
+def _gemm_tune(x, w, out, bias, resid, M, N, K, epi, ws, iters=8, w8=None):
     """Times every (tile shape, schedule) candidate on the real operands and keeps the fastest (all write the same result).
     In the decode step a projection's weights always come from HBM (13 GB of them stream through per step), so the timed launches
     rotate through enough copies of `w` that none is still in the 256-MiB Infinity Cache when its turn comes again: timed on ONE
-    hot copy the tuner preferred small macro tiles that then ran 10 % slower in place."""
-    n_copies = int(min(24, max(2, -(-640 * 2 ** 20 // (w.numel() * 2)))))
+    hot copy the tuner preferred small macro tiles that then ran 10 % slower in place.
+    w8 = (codes, scale): the GEMM on codes instead (w unused) - the candidates are those of W8_GEMM_TILES, the copies are copies of the
+    codes, and the result is None if the 8-bit entry serves none of them."""
+    src = w if w8 is None else w8[0]
+    n_copies = int(min(24, max(2, -(-640 * 2 ** 20 // (src.numel() * src.element_size())))))
     try:
-        copies = [w] + [w.clone() for _ in range(n_copies - 1)]
+        copies = [src] + [src.clone() for _ in range(n_copies - 1)]
     except torch.OutOfMemoryError:
-        copies = [w]
-    best, best_t = 1, float("inf")
+        copies = [src]
+    if w8 is None:
+        def call(wi, cfg):
+            _gemm_call(x, wi, out, bias, resid, M, N, K, epi, cfg, ws)
+            return True
+        candidates, best = GEMM_CANDIDATES, 1
+    else:
+        def call(ci, cfg):
+            return _gemm_w8_call(x, (ci, w8[1]), out, bias, M, N, K, epi, cfg, ws)
+        candidates, best = [(c, s_) for (c, s_) in GEMM_CANDIDATES if c in W8_GEMM_TILES], None
+    best_t = float("inf")
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     turn = 0
     # short launches (up to 128 rows: 30 - 60 us) are timed over up to six batches of `iters` launches, twice (the faster run counts):
@@ -896,33 +990,37 @@ def _gemm_tune(x, w, out, bias, resid, M, N, K, epi, ws, iters=8):
     flops = 2.0 * M * N * K * (2 if epi == EPI_SWIGLU else 1)
     short = M <= 128
     chunks, reps = (int(min(6, max(1, 2.5e-3 / max(flops / 1.0e15, 30e-6) / iters))), 2) if short else (1, 1)
-    for c, sch in GEMM_CANDIDATES:
+    for c, sch in candidates:
         if ((epi == EPI_SWIGLU and c in (5, 6, 7, 9, 13, 14, 16)) or (GEMM_BATCH_INVARIANT and sch != 1) or (c in (8, 9, 10, 11) and M > 256) or (c in (12, 13) and M > _SMALL_TILE_ROWS[0])
                 or (c in (14, 15) and M > _SMALL_TILE_ROWS[1]) or (c == 16 and M > 576)):
             continue
         if c in _GEMM_EXCLUDE:
             continue
         cfg = gemm_config(c, sch)
-        _gemm_call(x, copies[turn % len(copies)], out, bias, resid, M, N, K, epi, cfg, ws); turn += 1
+        if not call(copies[turn % len(copies)], cfg):
+            continue                                               # (the 8-bit entry does not serve this tile for this call)
+        turn += 1
         t = float("inf")
         for _rep in range(reps):
             tt = 0.0
             for _chunk in range(chunks):
                 e0.record()
                 for _ in range(iters):
-                    _gemm_call(x, copies[turn % len(copies)], out, bias, resid, M, N, K, epi, cfg, ws); turn += 1
+                    call(copies[turn % len(copies)], cfg); turn += 1
                 e1.record()
                 e1.synchronize()
                 tt += e0.elapsed_time(e1)
             t = min(t, tt)
         if t < best_t:
             best, best_t = cfg, t
-    _gemm_call(x, w, out, bias, resid, M, N, K, epi, best, ws)          # leave the caller's result in `out`
+    if best is not None:
+        call(src, best)                                                 # leave the caller's result in `out`
     return best
 
 
-def linear(x, w, out=None, bias=None):
-    """Row-batched projection: a weight-streaming kernel or the MFMA GEMM, whichever was measured faster for this (rows, N, K, dtype)."""
+def linear(x, w, out=None, bias=None, w8=None):
+    """Row-batched projection: a weight-streaming kernel or the MFMA GEMM, whichever was measured faster for this (rows, N, K, dtype).
+    w8: (codes, scale) of w - the GEMM on codes ("gemm8") joins the measurement, under a kind of its own."""
     M, K = x.shape
     N = w.shape[0]
     cands = {}
@@ -932,10 +1030,14 @@ def linear(x, w, out=None, bias=None):
         cands["gemm"] = lambda wi: gemm(x, wi)
     if not cands:
         raise ValueError(f"linear: no kernel serves M={M} N={N} K={K} (K % 128 == 0 and N % 4 == 0 for the GEMM)")
-    if _pick_form("linear", M, N, K, x, w, cands) == "skinny":
+    q = _w8_form_args(w, w8, M, K, N)
+    if q is not None:
+        cands["gemm8"] = lambda wi, qi: gemm(x, wi, w8=qi)
+    form = _pick_form("linear8" if q is not None else "linear", M, N, K, x, w, cands, w8=q)
+    if form == "skinny":
         y = skinny_gemm(x, w, out=out)
         return bias_act(y, bias, out=y) if bias is not None else y
-    return gemm(x, w, bias=bias, epi=EPI_BIAS if bias is not None else EPI_NONE, out=out)
+    return gemm(x, w, bias=bias, epi=EPI_BIAS if bias is not None else EPI_NONE, out=out, w8=q if form == "gemm8" else None)
 
 
 def _skinny_swiglu(x, w_gate_up, out=None):
@@ -947,7 +1049,7 @@ def _skinny_swiglu(x, w_gate_up, out=None):
     return out
 
 
-def swiglu_linear(x, w_gate_up, out=None):
+def swiglu_linear(x, w_gate_up, out=None, w8=None):
     """silu(x Wg^T) * (x Wu^T) with w_gate_up = [Wg; Wu]: one launch either way - the fused weight-streaming kernel (<= 16 rows: 8 features per
     block; 17 - 64: 16, gate + up tiles) or the MFMA GEMM with the SwiGLU epilogue (no [M, 2F] round trip, no silu_mul launch); measured."""
     M, K = x.shape
@@ -961,7 +1063,15 @@ def swiglu_linear(x, w_gate_up, out=None):
         cands["skinny"] = lambda wi, o=None: _skinny_swiglu(x, wi, o)
     if not cands:
         raise ValueError(f"swiglu_linear: no kernel serves M={M} F={F} K={K}")
-    form = _pick_form("swiglu", M, 2 * F, K, x, w_gate_up, {k: (lambda wi, f=f: f(wi)) for k, f in cands.items()})
+    q = _w8_form_args(w_gate_up, w8, M, K, 2 * F) if F % 128 == 0 else None      # (codes: the SwiGLU epilogue only)
+    if q is None:
+        form = _pick_form("swiglu", M, 2 * F, K, x, w_gate_up, {k: (lambda wi, f=f: f(wi)) for k, f in cands.items()})
+        return cands[form](w_gate_up, out)
+    timed = {k: (lambda wi, f=f: f(wi)) for k, f in cands.items()}
+    timed["gemm8"] = lambda wi, qi: gemm(x, wi, epi=EPI_SWIGLU, w8=qi)
+    form = _pick_form("swiglu8", M, 2 * F, K, x, w_gate_up, timed, w8=q)
+    if form == "gemm8":
+        return gemm(x, w_gate_up, epi=EPI_SWIGLU, out=out, w8=q)
     return cands[form](w_gate_up, out)
 
 
