@@ -225,6 +225,19 @@ int vdd_skinny_gemm_normed_w8(const void* H, const float* ss, int nss, const voi
 int vdd_skinny_swiglu_normed_w8(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W8_gate_up,
                                 const float* w_scale, void* act, int M, int F, int K, int64_t ldh, int dtype, void* hip_stream);
 
+/* The plain weight-streaming entries on 8-bit weight rows, M <= 64 and K % 256 == 0, the same bit-for-bit contract:
+ *   vdd_skinny_gemm_w8    Y = X . (w_scale[n] * code(W8[n, k]))^T: what vdd_skinny_gemm returns on w16 for a call without R and without
+ *                         slabs (n_split = 1), through each of its dispatch branches - 16-column blocks of eight or four waves up to 16
+ *                         rows, two / four MFMA row tiles at 17 - 32 / 33 - 64 rows, 32-column blocks for N > 8192 above 16 rows;
+ *   vdd_skinny_swiglu_w8  what vdd_skinny_swiglu returns on w16 (W8_gate_up [2F, K], w_scale [2F]: gate rows, then up rows; gate and up
+ *                         take their own scales before the first rounding).
+ * The residual and slab forms of vdd_skinny_gemm have no 8-bit twin.  M > 64 or K % 256 != 0 returns VDD_ERR_UNSUPPORTED and launches
+ * nothing: the caller runs the 16-bit twin on w16. */
+int vdd_skinny_gemm_w8(const void* X, const void* W8, const float* w_scale, void* Y, int M, int N, int K, int64_t ldx, int64_t ldy,
+                       int dtype, void* hip_stream);
+int vdd_skinny_swiglu_w8(const void* X, const void* W8_gate_up, const float* w_scale, void* act, int M, int F, int K, int64_t ldx,
+                         int dtype, void* hip_stream);
+
 /* The W-stream tiles of vdd_gemm (below) on 8-bit weight rows: Y[M,N] = epilogue(X[M,K] . (w_scale[n] * code(W8[n,k]))^T).
  * W8 is [N, K] bytes ([2N, K] for VDD_GEMM_SWIGLU: gate rows, then up rows), contiguous rows in the storage order above, w_scale
  * [N] ([2N]) fp32 powers of two, 16-byte aligned.  `config` has the bit layout of vdd_gemm's (tile id in bits 0-3 + 6-7, schedule in

@@ -684,31 +684,35 @@ __global__ void __launch_bounds__(NW * 64) skinny_gemm_kernel(const uint16_t* __
 // (B-fragment lanes ln < 8 -> row f0 + ln) and the 8 matching up columns (ln >= 8 -> row F + f0 + ln - 8), so the
 // epilogue finds gate and up of one feature in the same LDS tile: no [M, 2F] round trip and no silu_mul launch.
 // Rounding as the unfused pair: gate, up -> bf16; silu(gate) -> bf16; product -> bf16.
-__global__ void __launch_bounds__(256) skinny_swiglu_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W,
-                                                            uint16_t* __restrict__ A, int M, int F, int K, long long ldx) {
+// WV = RowsW8: W holds codes, wscale the 2F row scales (gate rows first); gate and up take their own scale before the first rounding.
+template <class WV = Rows16>
+__global__ void __launch_bounds__(256) skinny_swiglu_kernel(const uint16_t* __restrict__ X, const typename WV::code_t* __restrict__ W,
+                                                            uint16_t* __restrict__ A, int M, int F, int K, long long ldx,
+                                                            const float* __restrict__ wscale) {
     __shared__ float part[4][64][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int f0 = blockIdx.x * 8;
     const int ln = lane & 15, g = lane >> 4;
     const int kq = K / 4, kbeg = wave * kq;
     int f = f0 + (ln & 7); if (f >= F) f = F - 1;
-    const uint16_t* wp = W + ((size_t)(ln < 8 ? 0 : F) + f) * K + kbeg + g * 8;
+    const WV wp(W, (size_t)(ln < 8 ? 0 : F) + f, K, kbeg, g);
+    typedef typename WV::stage_t wstage_t;
     int r = ln; if (r >= M) r = M - 1;
     const uint16_t* xp = X + (size_t)r * ldx + kbeg + g * 8;
     f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
     constexpr int U = 8;             // two register stages, as in skinny_gemm_kernel
     const int nit = kq / (32 * U);
-    frag8_t b0[U], a0[U], b1[U], a1[U];
-    auto ld = [&](frag8_t (&b)[U], frag8_t (&a)[U], int kk) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) b[u] = ld_w(wp + (size_t)(kk + 32 * u));
+    wstage_t b0[U], b1[U];
+    frag8_t a0[U], a1[U];
+    auto ld = [&](wstage_t (&b)[U], frag8_t (&a)[U], int kk) {
+        wp.template ld<size_t>(b, kk);
 #pragma unroll
         for (int u = 0; u < U; ++u) a[u] = *reinterpret_cast<const frag8_t*>(xp + kk + 32 * u);
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto mm = [&](const frag8_t (&b)[U], const frag8_t (&a)[U]) {
+    auto mm = [&](const wstage_t (&b)[U], const frag8_t (&a)[U]) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc = mfma16(a[u], b[u], acc);
+        for (int u = 0; u < U; ++u) acc = mfma16(a[u], WV::frag(b[u]), acc);
         __builtin_amdgcn_sched_barrier(0);
     };
     if (nit > 0) ld(b0, a0, 0);
@@ -723,17 +727,20 @@ __global__ void __launch_bounds__(256) skinny_swiglu_kernel(const uint16_t* __re
     int k = nit * 32 * U;
     for (; k < kq; k += 32) {
         const frag8_t a = *reinterpret_cast<const frag8_t*>(xp + k);
-        acc = mfma16(a, *reinterpret_cast<const frag8_t*>(wp + (size_t)k), acc);
+        acc = mfma16(a, WV::frag(wp.template ld1<size_t>(k)), acc);
     }
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) part[wave][lane][rr] = acc[rr];
+    float sc0 = 1.f, sc1 = 1.f;      // 8-bit weights: the power-of-two scales of the finishing thread's gate and up rows
+    if constexpr (WV::SCALED) { int fc = f0 + (tid & 7); if (fc >= F) fc = F - 1; sc0 = wscale[fc]; sc1 = wscale[F + fc]; }
     __syncthreads();
     // C map: col = lane & 15, row = (lane >> 4) * 4 + rr.  Threads 0..127: (row = tid / 8, feature = tid % 8)
     if (tid < 128) {
         const int row = tid >> 3, c = tid & 7;
         if (row < M && f0 + c < F) {
             const int lg = (row >> 2) * 16 + c, lu = lg + 8, rr = row & 3;
-            const float gs = wave_partial_sum<4>(&part[0][lg][rr], 64 * 4), us = wave_partial_sum<4>(&part[0][lu][rr], 64 * 4);
+            float gs = wave_partial_sum<4>(&part[0][lg][rr], 64 * 4), us = wave_partial_sum<4>(&part[0][lu][rr], 64 * 4);
+            if constexpr (WV::SCALED) { gs *= sc0; us *= sc1; }
             A[(size_t)row * F + f0 + c] = swiglu_out(gs, us);
         }
     }
@@ -855,6 +862,122 @@ __global__ void __launch_bounds__(NW * 64) skinny_wide_kernel(const uint16_t* __
     }
 }
 
+// The 8-bit sibling of skinny_wide_kernel (without the residual): W holds e4m3 codes behind the RowsW8 view - a stage of U = 2 / 4 k-steps
+// is one / two 16-byte loads per column tile; K % 256 == 0 over four waves starts every wave slice on a group of 64 - and wscale the row
+// scales ([2N] for SWIGLU, gate rows first), multiplied onto the summed partials of each column tile before the first rounding.  The same
+// MFMAs in the same order as the 16-bit kernel.  A sibling and not a template parameter of it: behind the Rows16 view the 16-bit
+// kernel's address arithmetic compiled to another instruction order.
+template <int MT, int NW, bool SWIGLU>
+__global__ void __launch_bounds__(NW * 64) skinny_wide_w8_kernel(const uint16_t* __restrict__ X, const uint8_t* __restrict__ W,
+                                                                uint16_t* __restrict__ Y, int M, int N, int K, long long ldx, long long ldy,
+                                                                const float* __restrict__ wscale) {
+    typedef RowsW8 WV;
+    extern __shared__ __attribute__((aligned(16))) float wide_part[];            // [NW][MT][2][64][4]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ln = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * (SWIGLU ? 16 : 32);                               // SWIGLU: N = F features, 16 per block
+    const int kq = K / NW, kbeg = wave * kq;
+    auto wrow = [&](int c) {                                                      // this lane's W row of column tile c
+        int row = SWIGLU ? n0 + ln : n0 + 16 * c + ln;
+        if (row >= N) row = N - 1;
+        return (size_t)(SWIGLU && c == 1 ? N : 0) + row;
+    };
+    const WV wp[2] = {WV(W, wrow(0), K, kbeg, g), WV(W, wrow(1), K, kbeg, g)};
+    typedef typename WV::stage_t wstage_t;
+    const uint16_t* xp[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) { int r = t * 16 + ln; if (r >= M) r = M - 1; xp[t] = X + (size_t)r * ldx + kbeg + g * 8; }
+    f32x4_t acc[MT][2];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) { acc[t][0] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc[t][1] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
+    constexpr int U = MT >= 4 ? 2 : 4;           // k-steps per register stage (64 rows: 2 x (2 + 4) fragments x 2 stages + 32 accumulators fill the file)
+    const int nit = kq / (32 * U);
+    wstage_t b0[2][U], b1[2][U];
+    frag8_t a0[U][MT], a1[U][MT];
+    auto ld = [&](wstage_t (&b)[2][U], frag8_t (&a)[U][MT], int kk) {
+        wp[0].template ld<int>(b[0], kk); wp[1].template ld<int>(b[1], kk);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int t = 0; t < MT; ++t) a[u][t] = *reinterpret_cast<const frag8_t*>(xp[t] + kk + 32 * u);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto mm = [&](const wstage_t (&b)[2][U], const frag8_t (&a)[U][MT]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const frag8_t w0 = WV::frag(b[0][u]), w1 = WV::frag(b[1][u]);
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+                acc[t][0] = mfma16(a[u][t], w0, acc[t][0]);
+                acc[t][1] = mfma16(a[u][t], w1, acc[t][1]);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    if (nit > 0) ld(b0, a0, 0);
+    int it = 0;
+    for (; it + 2 <= nit; it += 2) {
+        ld(b1, a1, (it + 1) * 32 * U);
+        mm(b0, a0);
+        if (it + 2 < nit) ld(b0, a0, (it + 2) * 32 * U);
+        mm(b1, a1);
+    }
+    if (it < nit) mm(b0, a0);
+    const int krem = nit * 32 * U;
+    if (krem < kq) {            // the slice's ragged tail (11008 / 8 = 1376 = 10 batches + 96): one more batch, k-steps beyond it with zero W
+        const wstage_t zero = WV::zero();
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int kk = krem + 32 * u, kc = kk < kq ? kk : krem;
+            b0[0][u] = wp[0].template ld1<int>(kc); b0[1][u] = wp[1].template ld1<int>(kc);
+#pragma unroll
+            for (int t = 0; t < MT; ++t) a0[u][t] = *reinterpret_cast<const frag8_t*>(xp[t] + kc);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) if (krem + 32 * u >= kq) { b0[0][u] = zero; b0[1][u] = zero; }
+        mm(b0, a0);
+    }
+    auto part = [&](int w, int t, int c) { return wide_part + ((((size_t)w * MT + t) * 2 + c) * 64) * 4; };
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) *reinterpret_cast<f32x4_t*>(part(wave, t, c) + lane * 4) = acc[t][c];
+    const float scw[2] = {wscale[wrow(0)], wscale[wrow(1)]};                     // the power-of-two scales of this lane's column in either tile
+    __syncthreads();
+    // C/D map of 16x16x32: col = lane & 15, row = (lane >> 4) * 4 + r.  The NW partials of an entry are added in wave order (fixed).
+    auto total = [&](int t, int c) {
+        f32x4_t s = *reinterpret_cast<const f32x4_t*>(part(0, t, c) + lane * 4);
+#pragma unroll
+        for (int w = 1; w < NW; ++w) { const f32x4_t v = *reinterpret_cast<const f32x4_t*>(part(w, t, c) + lane * 4); s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3]; }
+        return s;
+    };
+    if constexpr (SWIGLU) {
+        for (int t = wave; t < MT; t += NW) {
+            f32x4_t gs = total(t, 0), us = total(t, 1);
+            gs[0] *= scw[0]; gs[1] *= scw[0]; gs[2] *= scw[0]; gs[3] *= scw[0];
+            us[0] *= scw[1]; us[1] *= scw[1]; us[2] *= scw[1]; us[3] *= scw[1];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = t * 16 + g * 4 + r, col = n0 + ln;
+                if (row < M && col < N) Y[(size_t)row * ldy + col] = swiglu_out(gs[r], us[r]);
+            }
+        }
+    } else {
+        for (int tc = wave; tc < MT * 2; tc += NW) {
+            const int t = tc >> 1, c = tc & 1;
+            f32x4_t sv = total(t, c);
+            const float sc = c ? scw[1] : scw[0];
+            sv[0] *= sc; sv[1] *= sc; sv[2] *= sc; sv[3] *= sc;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = t * 16 + g * 4 + r, col = n0 + 16 * c + ln;
+                if (row < M && col < N) Y[(size_t)row * ldy + col] = (uint16_t)f2e(sv[r]);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ launch helpers of the weight-streaming entries
 // compute units of the current device (256 where it cannot be asked), asked once per process
 static int cu_count() {
@@ -887,6 +1010,23 @@ static void wide_launch(const uint16_t* x, const uint16_t* w, const uint16_t* r,
     } while (0)
     if (mt == 2) VDD_WIDE(2, 4, SWIGLU); else if (mt == 3) VDD_WIDE(3, 4, SWIGLU); else VDD_WIDE(4, 4, SWIGLU);
 #undef VDD_WIDE
+}
+
+// ... and its 8-bit sibling
+template <bool SWIGLU>
+static void wide_w8_launch(const uint16_t* x, const uint8_t* w, const float* wscale, uint16_t* y, int M, int N, int K, int64_t ldx, int64_t ldy,
+                           hipStream_t st) {
+    const int mt = (M + 15) / 16;
+    const dim3 g2(SWIGLU ? (N + 15) / 16 : (N + 31) / 32);
+#define VDD_WIDE_W8(MT, NW, SWIGLU)                                                                                                    \
+    do {                                                                                                                               \
+        constexpr int smem = NW * MT * 2 * 64 * 4 * (int)sizeof(float);                                                                \
+        static bool attr = false;                                                                                                      \
+        if (!attr) { (void)hipFuncSetAttribute((const void*)skinny_wide_w8_kernel<MT, NW, SWIGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr = true; } \
+        hipLaunchKernelGGL((skinny_wide_w8_kernel<MT, NW, SWIGLU>), g2, dim3(NW * 64), smem, st, x, w, y, M, N, K, (long long)ldx, (long long)ldy, wscale); \
+    } while (0)
+    if (mt == 2) VDD_WIDE_W8(2, 4, SWIGLU); else if (mt == 3) VDD_WIDE_W8(3, 4, SWIGLU); else VDD_WIDE_W8(4, 4, SWIGLU);
+#undef VDD_WIDE_W8
 }
 
 // the d-wide projections of the small-M decoder layer (SSOUT of skinny_gemm_kernel): 16-bit or 8-bit weight rows
@@ -1051,8 +1191,8 @@ VDD_HIDDEN int VDD_IMPL(vdd_skinny_swiglu)(const void* X, const void* W_gate_up,
     if (M > 16)                                                             // 17 - 64 rows: 16 features (gate + up tiles) per block
         wide_launch<true>((const uint16_t*)X, (const uint16_t*)W_gate_up, nullptr, (uint16_t*)act, M, F, K, ldx, 0, (int64_t)F, (hipStream_t)stream);
     else
-        hipLaunchKernelGGL(skinny_swiglu_kernel, dim3((F + 7) / 8), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)X,
-                           (const uint16_t*)W_gate_up, (uint16_t*)act, M, F, K, (long long)ldx);
+        hipLaunchKernelGGL(skinny_swiglu_kernel<Rows16>, dim3((F + 7) / 8), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)X,
+                           (const uint16_t*)W_gate_up, (uint16_t*)act, M, F, K, (long long)ldx, (const float*)nullptr);
     return ok(hipSuccess);
 }
 
@@ -1104,6 +1244,41 @@ VDD_HIDDEN int VDD_IMPL(vdd_skinny_swiglu_normed_w8)(const void* H, const float*
     if (!H || !ss || nss <= 0 || (nss % 4) != 0 || !ln_w || !W8_gate_up || !w_scale || !act || (ldh % 8) != 0) return VDD_ERR_INVALID_ARG;
     if (M > 16 || K <= 0 || K % 256 != 0) return VDD_ERR_UNSUPPORTED;
     return normed_launch<true, RowsW8>(H, ss, nss, ln_w, eps, W8_gate_up, w_scale, act, M, F, K, ldh, (int64_t)F, (F + 7) / 8, stream);
+}
+
+// ---- the plain weight-streaming entries on 8-bit weight rows: every dispatch branch vdd_skinny_gemm / vdd_skinny_swiglu take for a call
+// without residual and without slabs, bit for bit the 16-bit entry on w16.  M > 64 or K % 256 != 0 is VDD_ERR_UNSUPPORTED (nothing launched).
+VDD_HIDDEN int VDD_IMPL(vdd_skinny_gemm_w8)(const void* X, const void* W8, const float* w_scale, void* Y, int M, int N, int K, int64_t ldx, int64_t ldy,
+                       void* stream) {
+    if (M <= 0 || N <= 0) return VDD_OK;
+    if (!X || !W8 || !w_scale || !Y || (ldx % 8) != 0) return VDD_ERR_INVALID_ARG;
+    if (M > 64 || K <= 0 || K % 256 != 0) return VDD_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid((N + 15) / 16, 1);
+    auto x = (const uint16_t*)X; auto w = (const uint8_t*)W8; auto y = (uint16_t*)Y;
+    if (M > 16 && N > 8192) {
+        wide_w8_launch<false>(x, w, w_scale, y, M, N, K, ldx, ldy, st);
+        return ok(hipSuccess);
+    }
+#define VDD_SKINNY_W8(MT, NW) hipLaunchKernelGGL((skinny_gemm_kernel<MT, NW, false, RowsW8>), grid, dim3(NW * 64), 0, st, x, w, (const uint16_t*)nullptr, y, (float*)nullptr, M, N, K, (long long)ldx, 0ll, (long long)ldy, (float*)nullptr, w_scale)
+    if (M <= 16 && N <= 8192 && eight_wave_blocks(N)) VDD_SKINNY_W8(1, 8);
+    else if (M <= 16) VDD_SKINNY_W8(1, 4);
+    else if (M <= 32) VDD_SKINNY_W8(2, 4); else VDD_SKINNY_W8(4, 4);
+#undef VDD_SKINNY_W8
+    return ok(hipSuccess);
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_skinny_swiglu_w8)(const void* X, const void* W8_gate_up, const float* w_scale, void* act, int M, int F, int K, int64_t ldx,
+                         void* stream) {
+    if (M <= 0 || F <= 0) return VDD_OK;
+    if (!X || !W8_gate_up || !w_scale || !act || (ldx % 8) != 0) return VDD_ERR_INVALID_ARG;
+    if (M > 64 || K <= 0 || K % 256 != 0) return VDD_ERR_UNSUPPORTED;
+    if (M > 16)
+        wide_w8_launch<true>((const uint16_t*)X, (const uint8_t*)W8_gate_up, w_scale, (uint16_t*)act, M, F, K, ldx, (int64_t)F, (hipStream_t)stream);
+    else
+        hipLaunchKernelGGL(skinny_swiglu_kernel<RowsW8>, dim3((F + 7) / 8), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)X,
+                           (const uint8_t*)W8_gate_up, (uint16_t*)act, M, F, K, (long long)ldx, w_scale);
+    return ok(hipSuccess);
 }
 
 }  // extern "C"

@@ -67,6 +67,12 @@ VDD_MODEL_FN(vdd_skinny_swiglu_normed_w8,
              VDD_P(const void* H, const float* ss, int nss, const void* ln_w, float eps, const void* W8_gate_up, const float* w_scale, void* act, int M, int F,
                    int K, int64_t ldh),
              VDD_P(H, ss, nss, ln_w, eps, W8_gate_up, w_scale, act, M, F, K, ldh))
+VDD_MODEL_FN(vdd_skinny_gemm_w8,
+             VDD_P(const void* X, const void* W8, const float* w_scale, void* Y, int M, int N, int K, int64_t ldx, int64_t ldy),
+             VDD_P(X, W8, w_scale, Y, M, N, K, ldx, ldy))
+VDD_MODEL_FN(vdd_skinny_swiglu_w8,
+             VDD_P(const void* X, const void* W8_gate_up, const float* w_scale, void* act, int M, int F, int K, int64_t ldx),
+             VDD_P(X, W8_gate_up, w_scale, act, M, F, K, ldx))
 VDD_MODEL_FN(vdd_gemm,
              VDD_P(const void* X, const void* W, void* Y, const void* bias, const void* resid, int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldy,
                    int64_t ldr, int epilogue, int config, void* workspace, int64_t workspace_bytes),

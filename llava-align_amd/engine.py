@@ -603,7 +603,7 @@ class LanguageModel:
         normalised input (qkv, gate/up, lm_head) normalise it as it loads (ops.linear_resid_ss / linear_normed): the two 6.8-us
         RMSNorm launches of a layer - a tenth of a one-question step - are gone; only layer 0 normalises the embeddings with the
         stand-alone kernel.  Weights quantised by LlavaWeights.quantize_lm_w8 are streamed as 8-bit codes while ops.W8_DECODE is on
-        (layer 0's qkv, a plain ops.linear, reads w16): the same bits either way."""
+        (layer 0's qkv, a plain ops.linear, only inside the form its 16-bit run takes - `keep_bits`): the same bits either way."""
         c, t, w8 = self.cfg, self.w.t, self.w.w8
         H, Hkv, D = c.n_heads, c.n_kv_heads, c.head_dim
         ss = None
@@ -611,7 +611,7 @@ class LanguageModel:
             p = f"l{i}."
             bias = t[p + "bqkv_lm"] if c.qkv_bias else None
             if ss is None:
-                qkv = ops.linear(ops.rmsnorm(resid, t[p + "ln1"], c.eps), t[p + "wqkv"], bias=bias)
+                qkv = ops.linear(ops.rmsnorm(resid, t[p + "ln1"], c.eps), t[p + "wqkv"], bias=bias, w8=w8(p + "wqkv"), keep_bits=True)
             else:
                 qkv = ops.linear_normed(resid, ss, t[p + "ln1"], c.eps, t[p + "wqkv"], bias=bias, w8=w8(p + "wqkv"))
             att = ops.decode_attention_fused(qkv, pos, cpos, slot, self.cs, kv.ko[i], kv.vo[i], attn_rows, H, Hkv, D,

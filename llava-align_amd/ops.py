@@ -43,6 +43,8 @@ _SIGS = {
     "vdd_skinny_gemm_normed_w8": [_P, _P, _I, _P, _F, _P, _P, _P, _I, _I, _I, _L, _L, _I, _P],
     "vdd_skinny_swiglu_normed_w8": [_P, _P, _I, _P, _F, _P, _P, _P, _I, _I, _I, _L, _I, _P],
     "vdd_gemm_w8": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _I, _I, _P, _L, _I, _P],
+    "vdd_skinny_gemm_w8": [_P, _P, _P, _P, _I, _I, _I, _L, _L, _I, _P],
+    "vdd_skinny_swiglu_w8": [_P, _P, _P, _P, _I, _I, _I, _L, _I, _P],
     "vdd_rope_kv_write_paged": [_P] * 9 + [_I, _I, _I, _I, _L, _I, _I, _I, _I, _P],
     "vdd_decode_attention_paged": [_P] * 9 + [_I, _I, _I, _I, _L, _I, _I, _I, _L, _I, _I, _F, _I, _P],
     "vdd_kv_pages_scatter": [_P] * 7 + [_I, _I, _I, _I, _L, _I, _L, _I, _I, _I, _I, _P],
@@ -180,10 +182,13 @@ def embed_scatter(ids, rows, table, out):
     return out
 
 
-def skinny_gemm(x, w, resid=None, out=None, n_split=1, slabs=False):
+def skinny_gemm(x, w, resid=None, out=None, n_split=1, slabs=False, w8=None):
     """x [M<=64, K] @ w[N, K]^T (+ resid [M, N]) -> [M, N]; streams w from HBM exactly once.
-    slabs=True: returns the fp32 split-K partials [n_split, M, N] instead (feed them to rmsnorm as `delta`)."""
+    slabs=True: returns the fp32 split-K partials [n_split, M, N] instead (feed them to rmsnorm as `delta`).
+    w8: (codes, scale) of w (quantize_w8) - the plain product streams them instead where vdd_skinny_gemm_w8 serves the call (K % 256 == 0;
+    the same bits); with resid or slabs, w16 as ever."""
     N = w.shape[0]
+    q = _w8_args(w, w8)
     fn = _lib_ready().vdd_skinny_gemm
     dt = _dt(x, w, resid)
     M, K = x.shape
@@ -192,6 +197,9 @@ def skinny_gemm(x, w, resid=None, out=None, n_split=1, slabs=False):
         _lib.check(fn(x.data_ptr(), w.data_ptr(), None, None, out.data_ptr(), n_split, M, N, K, x.stride(0), 0, N, dt, _st(x)))
         return out
     out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+    if q is not None and resid is None and _w8_done(_lib_ready().vdd_skinny_gemm_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, N, K,
+                                                                                     x.stride(0), out.stride(0), dt, _st(x))):
+        return out
     _lib.check(fn(x.data_ptr(), w.data_ptr(), resid.data_ptr() if resid is not None else None,
                   out.data_ptr(), None, 1, M, N, K, x.stride(0), resid.stride(0) if resid is not None else 0,
                   out.stride(0), dt, _st(x)))
@@ -241,7 +249,8 @@ def linear_to_norm(x, w, w8=None):
     workgroups and put together by ONE that reads the others' partial tiles in turn, as slabs nobody waits; the weight-streaming kernel
     re-reads X per column block and, when N / 16 column blocks do not divide over the CUs (d = 5120: 320 blocks on 256), runs a second
     round for a quarter of the chip.
-    w8: (codes, scale) of w - the GEMM and the slabs on codes ("gemm8", "slabs8") join the measurement, under a kind of its own."""
+    w8: (codes, scale) of w - the GEMM, the slabs and the weight-streaming kernel on codes ("gemm8", "slabs8", "skinny8") join the
+    measurement, under a kind of its own."""
     M, K = x.shape
     N = w.shape[0]
     cands = {}
@@ -257,17 +266,24 @@ def linear_to_norm(x, w, w8=None):
         cands["gemm8"] = lambda wi, qi: gemm(x, wi, w8=qi)
         if s_:
             cands["slabs8"] = lambda wi, qi: gemm_slabs(x, wi, s_, w8=qi)
-    form = _pick_form("to_norm8" if q is not None else "to_norm", M, N, K, x, w, cands, consumer="norm", w8=q)
+    qs = _w8_skinny_args(w, w8, M, K) if "skinny" in cands else None
+    if qs is not None:
+        cands["skinny8"] = lambda wi, qi: skinny_gemm(x, wi, w8=qi)
+    q8 = q if q is not None else qs
+    form = _pick_form("to_norm8" if q8 is not None else "to_norm", M, N, K, x, w, cands, consumer="norm", w8=q8)
     if form in ("slabs", "slabs8"):
         return gemm_slabs(x, w, s_, w8=q if form == "slabs8" else None)
-    return skinny_gemm(x, w) if form == "skinny" else gemm(x, w, w8=q if form == "gemm8" else None)
+    if form in ("skinny", "skinny8"):
+        return skinny_gemm(x, w, w8=qs if form == "skinny8" else None)
+    return gemm(x, w, w8=q if form == "gemm8" else None)
 
 
 NORM_FUSED_MAX_M = 16   # rows up to which the normalise-once projections EXIST (their LDS image of the normalised rows; see norm_fused_rows)
 
 
-FORCE_FORM = {}             # tests / probes: kind ("linear", "to_norm", "swiglu"; "linear8", "to_norm8", "swiglu8" with codes) -> "skinny" | "gemm" |
-                            # "slabs" | "gemm8" | "slabs8" wins whenever it is eligible
+FORCE_FORM = {}             # tests / probes: kind ("linear", "to_norm", "swiglu"; "linear8", "to_norm8", "swiglu8" with codes; those three + "i" in
+                            # batch-invariant mode: "gemm" | "gemm8" only; "linear8t" of linear(keep_bits=True): "skinny" | "skinny8" only) -> "skinny" | "gemm" | "slabs" | "gemm8" | "slabs8" | "skinny8" wins
+                            # whenever it is eligible
 FORCE_LAYER_FORM = None     # tests / probes: "fused" | "plain" for every row count the fused layer serves
 
 
@@ -416,10 +432,20 @@ W8_GEMM_MAX_M = 256
 
 
 def _w8_form_args(w, w8, M, K, N):
-    """(codes, scale) if the 8-bit GEMM forms are candidates for this projection: codes given, the switch on, not the batch-invariant mode
-    (one form per op there), M <= W8_GEMM_MAX_M and a shape the GEMM takes."""
+    """(codes, scale) if the 8-bit GEMM forms are candidates for this projection: codes given, the switch on, M <= W8_GEMM_MAX_M and a
+    shape the GEMM takes.  In batch-invariant mode too: there `_pick_form` keeps "gemm8" alone of the 8-bit forms, and the GEMM on codes
+    is tuned among the W-stream tiles on the data-parallel schedule - the bits of "gemm" on w16 with any tile on that schedule."""
     q = _w8_args(w, w8)
-    if q is None or GEMM_BATCH_INVARIANT or M > W8_GEMM_MAX_M or K % 128 != 0 or N % 4 != 0:
+    if q is None or M > W8_GEMM_MAX_M or K % 128 != 0 or N % 4 != 0:
+        return None
+    return q
+
+
+def _w8_skinny_args(w, w8, M, K):
+    """(codes, scale) if the weight-streaming kernels on codes ("skinny8") are a candidate: codes given, the switch on, a shape the 16-bit
+    kernels take and the 8-bit entries serve (K % 256 == 0), never in batch-invariant mode."""
+    q = _w8_args(w, w8)
+    if q is None or GEMM_BATCH_INVARIANT or not _skinny_serves(M, K) or K % 256 != 0:
         return None
     return q
 
@@ -489,6 +515,7 @@ def swiglu_linear_normed(h, ss, ln_w, eps, w_gate_up, out=None, w8=None):
 # (form_choices_mi355x.json, generated by tools/form_sweep.py for the 7B / 13B / Qwen-VL shapes) are such measurements.
 FALLBACK_SKINNY_ROWS = 16   # no measurement available (graph capture in progress, GEMM_AUTOTUNE off): weight-streaming up to one MFMA row tile,
 FALLBACK_FUSED_ROWS = 8     # the GEMM above; norm-fused layer up to 8 rows - shape-generic, deliberately not a tuned number
+INVARIANT_KIND_SUFFIX = "i" # batch-invariant mode with codes: "gemm" against "gemm8" under the kinds "linear8i", "to_norm8i", "swiglu8i"
 _form_choice = {}           # (kind, rows or 64-row bucket, N, K, dtype) -> "skinny" | "gemm" | "slabs";  ("layer", rows, d, 0, dtype) -> "fused" | "plain"
 
 
@@ -569,7 +596,11 @@ def _pick_form(kind, M, N, K, x, w, cands, consumer=None, w8=None):
     partials: cheaper projection, dearer norm).  w8 = (codes, scale): the candidates whose name ends in "8" are fn(weight, (codes, scale))
     and are timed on rotating copies of the codes."""
     if GEMM_BATCH_INVARIANT and "gemm" in cands:
-        return "gemm"
+        # one summation order per output element: the GEMM's data-parallel schedule - on w16 or, where measured faster, on the codes (the
+        # same bits: a W-stream tile on that schedule).  Measured under a kind of its own (kind + "i"): no tuned-mode entry shares the key
+        if "gemm8" not in cands:
+            return "gemm"
+        cands, kind, consumer = {"gemm": cands["gemm"], "gemm8": cands["gemm8"]}, kind + INVARIANT_KIND_SUFFIX, None
     if len(cands) == 1:
         return next(iter(cands))
     if FORCE_FORM.get(kind) in cands:
@@ -742,9 +773,7 @@ def _gemm_key_w8(M, N, K, epi, dt):
 def _gemm_w8_config(x, q, out, bias, M, N, K, epi, dt, ws):
     """Tile / schedule of the GEMM on codes for this shape: the process table, the cache file, or a timing run now; None where it cannot be
     measured here (the tuner off, a capture in progress) or no W-stream tile serves the call - the caller runs the 16-bit GEMM."""
-    if GEMM_BATCH_INVARIANT:
-        return None
-    key = _gemm_key_w8(M, N, K, epi, dt)
+    key = _gemm_key_w8(M, N, K, epi, dt)                   # (carries the batch-invariant flag: that mode tunes schedule 1 alone)
     config = _gemm_choice.get(key)
     if config is None and GEMM_AUTOTUNE:
         _load_persisted(x.device)
@@ -1018,9 +1047,12 @@ def _gemm_tune(x, w, out, bias, resid, M, N, K, epi, ws, iters=8, w8=None):
     return best
 
 
-def linear(x, w, out=None, bias=None, w8=None):
+def linear(x, w, out=None, bias=None, w8=None, keep_bits=False):
     """Row-batched projection: a weight-streaming kernel or the MFMA GEMM, whichever was measured faster for this (rows, N, K, dtype).
-    w8: (codes, scale) of w - the GEMM on codes ("gemm8") joins the measurement, under a kind of its own."""
+    w8: (codes, scale) of w - the GEMM and the weight-streaming kernel on codes ("gemm8", "skinny8") join the measurement, under a kind of
+    its own.  Forms differ in their summation order, so that measurement may return other low-order bits than the call without codes.
+    keep_bits: the codes may only replace w16 INSIDE the form the call without codes takes - where that is "skinny", the twin "skinny8" if
+    measured faster (kind "linear8t": a pair with the same bits) - for a caller that promises the bits of its 16-bit run (the few-row step)."""
     M, K = x.shape
     N = w.shape[0]
     cands = {}
@@ -1031,20 +1063,33 @@ def linear(x, w, out=None, bias=None, w8=None):
     if not cands:
         raise ValueError(f"linear: no kernel serves M={M} N={N} K={K} (K % 128 == 0 and N % 4 == 0 for the GEMM)")
     q = _w8_form_args(w, w8, M, K, N)
-    if q is not None:
-        cands["gemm8"] = lambda wi, qi: gemm(x, wi, w8=qi)
-    form = _pick_form("linear8" if q is not None else "linear", M, N, K, x, w, cands, w8=q)
-    if form == "skinny":
-        y = skinny_gemm(x, w, out=out)
+    qs = _w8_skinny_args(w, w8, M, K) if "skinny" in cands else None
+    if keep_bits and (q is not None or qs is not None):
+        form, q = _pick_form("linear", M, N, K, x, w, cands), None
+        if form == "skinny" and qs is not None:
+            form = _pick_form("linear8t", M, N, K, x, w, {"skinny": cands["skinny"], "skinny8": lambda wi, qi: skinny_gemm(x, wi, w8=qi)}, w8=qs)
+    else:
+        if q is not None:
+            cands["gemm8"] = lambda wi, qi: gemm(x, wi, w8=qi)
+        if qs is not None:
+            cands["skinny8"] = lambda wi, qi: skinny_gemm(x, wi, w8=qi)
+        q8 = q if q is not None else qs
+        form = _pick_form("linear8" if q8 is not None else "linear", M, N, K, x, w, cands, w8=q8)
+    if form in ("skinny", "skinny8"):
+        y = skinny_gemm(x, w, out=out, w8=qs if form == "skinny8" else None)
         return bias_act(y, bias, out=y) if bias is not None else y
     return gemm(x, w, bias=bias, epi=EPI_BIAS if bias is not None else EPI_NONE, out=out, w8=q if form == "gemm8" else None)
 
 
-def _skinny_swiglu(x, w_gate_up, out=None):
+def _skinny_swiglu(x, w_gate_up, out=None, w8=None):
     M, K = x.shape
     F = w_gate_up.shape[0] // 2
+    q = _w8_args(w_gate_up, w8)
     dt = _dt(x, w_gate_up)
     out = torch.empty(M, F, dtype=x.dtype, device=x.device) if out is None else out
+    if q is not None and _w8_done(_lib_ready().vdd_skinny_swiglu_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, F, K, x.stride(0),
+                                                                     dt, _st(x))):
+        return out
     _lib.check(_lib_ready().vdd_skinny_swiglu(x.data_ptr(), w_gate_up.data_ptr(), out.data_ptr(), M, F, K, x.stride(0), dt, _st(x)))
     return out
 
@@ -1063,15 +1108,22 @@ def swiglu_linear(x, w_gate_up, out=None, w8=None):
         cands["skinny"] = lambda wi, o=None: _skinny_swiglu(x, wi, o)
     if not cands:
         raise ValueError(f"swiglu_linear: no kernel serves M={M} F={F} K={K}")
-    q = _w8_form_args(w_gate_up, w8, M, K, 2 * F) if F % 128 == 0 else None      # (codes: the SwiGLU epilogue only)
-    if q is None:
+    _w8_args(w_gate_up, w8)                                                       # (a malformed pair raises whatever the shape)
+    q = _w8_form_args(w_gate_up, w8, M, K, 2 * F) if F % 128 == 0 else None      # (the GEMM on codes: the SwiGLU epilogue only)
+    qs = _w8_skinny_args(w_gate_up, w8, M, K) if "skinny" in cands else None
+    if q is None and qs is None:
         form = _pick_form("swiglu", M, 2 * F, K, x, w_gate_up, {k: (lambda wi, f=f: f(wi)) for k, f in cands.items()})
         return cands[form](w_gate_up, out)
     timed = {k: (lambda wi, f=f: f(wi)) for k, f in cands.items()}
-    timed["gemm8"] = lambda wi, qi: gemm(x, wi, epi=EPI_SWIGLU, w8=qi)
-    form = _pick_form("swiglu8", M, 2 * F, K, x, w_gate_up, timed, w8=q)
+    if q is not None:
+        timed["gemm8"] = lambda wi, qi: gemm(x, wi, epi=EPI_SWIGLU, w8=qi)
+    if qs is not None:
+        timed["skinny8"] = lambda wi, qi: _skinny_swiglu(x, wi, w8=qi)
+    form = _pick_form("swiglu8", M, 2 * F, K, x, w_gate_up, timed, w8=q if q is not None else qs)
     if form == "gemm8":
         return gemm(x, w_gate_up, epi=EPI_SWIGLU, out=out, w8=q)
+    if form == "skinny8":
+        return _skinny_swiglu(x, w_gate_up, out, w8=qs)
     return cands[form](w_gate_up, out)
 
 

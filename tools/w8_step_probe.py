@@ -5,16 +5,23 @@
         seven-launch layer, where the GEMM's W-stream tiles read the codes): ms per captured decode step from the
         engine's HIP events (VddLlavaEngine.call_timing).  The two legs ALTERNATE in one process: "w16" is an unquantised engine with
         ops.W8_DECODE off - the path of a build without this feature - and "w8" a load_8bit engine over the same random weights.  One JSON
-        line per (shape, rows) with the per-leg medians, the spread, the layer form each leg took and the bytes a step streams.
+        line per (shape, rows, mode) with the per-leg medians, the spread of the repeated 16-bit runs (`w16_spread_ms` = max - min) and
+        whether the 8-bit step is slower than its 16-bit leg by more than that (`w8_slower_beyond_spread`), the layer form each leg took, the
+        projection forms the 8-bit leg measured and the bytes a step streams.  Two modes per row count: "tuned" (sampled decode, every form
+        measured) and "invariant" (`ops.batch_invariant()`, cd_greedy - what the drivers select for every deterministic decode: the GEMM's
+        data-parallel schedule on w16 or, where measured faster, on the codes).  `--modes tuned|invariant` and `--rows 2,24,...` restrict.
     python tools/w8_step_probe.py --proj [7b] [13b] [--out profiles/w8_decode_step.jsonl]
         the projections of one layer alone at 24, 36, 64, 128, 256 rows - `to_norm` (o, down), `linear` (qkv, lm_head), `swiglu` (gate/up) -
         through the ops wrappers, 16-bit (w8=None) against 8-bit (w8=codes), each in the form its tuner measured; cold weights by rotation
-        through copies as ops._time_thunks does; the legs alternate and the 16-bit leg is repeated, so its spread is in the record.
+        through copies as ops._time_thunks does; the legs alternate and the 16-bit leg is repeated, so its spread is in the record.  Up to
+        64 rows the record also holds the weight-streaming kernels alone, forced: "skinny" on w16 against "skinny8" on the codes
+        (`skinny_us`, `skinny8_us`).
     python tools/w8_step_probe.py --trace 7b
         one leg-w8 and one leg-w16 decode at 2 rows, nothing else: the workload for a kernel trace taken in a run of its own,
             timeout 600 rocprofv3 --kernel-trace --stats -d profiles/w8_trace -o w8 -- python tools/w8_step_probe.py --trace 7b
         whose kernel stats go to profiles/w8_kernel_stats.csv.
 No GPU: the script fails (there is nothing to measure on a CPU)."""
+import contextlib
 import json
 import os
 import statistics
@@ -58,15 +65,28 @@ def step_ms(eng, ids, kw, w8):
 
 
 def stream_bytes(eng, w8, rows=2):
-    """Weight bytes one step reads: 16-bit everywhere, or codes + scales where they can be streamed (layer 0's qkv of the few-row step stays
-    16-bit).  Above 16 rows this is the count with EVERY projection on codes; the forms the tuner really took are in the record."""
+    """Weight bytes one step reads: 16-bit everywhere, or codes + scales with EVERY projection on codes; the forms the tuner really took
+    are in the record."""
     n = 0
     for k, t in eng.w.t.items():
         if k.endswith((".w8", ".w8s")) or not ((k.startswith("l") and k[1].isdigit()) or k in ("norm", "lm_head")):
             continue
-        coded = w8 and eng.w.w8(k) is not None and (k != "l0.wqkv" or rows > 16)
+        coded = w8 and eng.w.w8(k) is not None
         n += t.numel() * (1 if coded else 2) + (t.shape[0] * 4 if coded else 0)
     return n
+
+
+@contextlib.contextmanager
+def _forced(forms):
+    """ops.FORCE_FORM = forms for the duration"""
+    old = dict(ops.FORCE_FORM)
+    ops.FORCE_FORM.clear()
+    ops.FORCE_FORM.update(forms)
+    try:
+        yield
+    finally:
+        ops.FORCE_FORM.clear()
+        ops.FORCE_FORM.update(old)
 
 
 def _time_rot(fn, n_rot, iters=16):
@@ -107,6 +127,16 @@ def proj_leg(name, out):
                        w16_form=ops._form_choice.get(ops._form_key(kind, rows, N, K, dt)), w8_form=ops._form_choice.get(ops._form_key(kind + "8", rows, N, K, dt)),
                        w16_mb=round(N * K * 2 / 1e6, 1), w8_mb=round((N * K + N * 4) / 1e6, 1))
             rec["speedup"] = round(rec["w16_us"] / rec["w8_us"], 3)
+            if ops._skinny_serves(rows, K) and K % 256 == 0:      # the weight-streaming kernels alone: "skinny" on w16 against "skinny8" on the codes
+                s16, s8 = [], []
+                for _ in range(REPS):
+                    with _forced({k: "skinny" for k in (kind, kind + "8")}):
+                        s16.append(_time_rot(lambda i: fn(x, w16s[i]), n_rot))
+                    with _forced({kind + "8": "skinny8"}):
+                        s8.append(_time_rot(lambda i: fn(x, w16s[i], w8=qs[i]), n_rot))
+                rec.update(skinny_us=round(statistics.median(s16) * 1e3, 2), skinny8_us=round(statistics.median(s8) * 1e3, 2),
+                           skinny_us_all=[round(v * 1e3, 2) for v in s16], skinny8_us_all=[round(v * 1e3, 2) for v in s8])
+                rec["skinny8_speedup"] = round(rec["skinny_us"] / rec["skinny8_us"], 3)
             rec["w16_tb_s"], rec["w8_tb_s"] = round(rec["w16_mb"] / rec["w16_us"], 2), round(rec["w8_mb"] / rec["w8_us"], 2)      # MB / us = TB / s
             line = json.dumps(rec)
             print(line, flush=True)
@@ -123,6 +153,8 @@ def main():
     layers = int(args[args.index("--layers") + 1]) if "--layers" in args else 0
     out = args[args.index("--out") + 1] if "--out" in args else None
     names = [a for a in args if a in SHAPES] or list(SHAPES)
+    modes = args[args.index("--modes") + 1].split(",") if "--modes" in args else ["tuned", "invariant"]
+    only_rows = {int(v) for v in args[args.index("--rows") + 1].split(",")} if "--rows" in args else set(ROWS)
     if not torch.cuda.is_available():
         raise SystemExit("w8_step_probe: no GPU - nothing can be measured here")
     if "--proj" in args:
@@ -133,6 +165,8 @@ def main():
         e16, e8 = engines(name, layers)
         lm = e16.cfg.lm
         for rows, (Q, nb) in ROWS.items():
+            if rows not in only_rows:
+                continue
             ids, imgs = pope_prompts(Q, per_img=1, seed=5, vocab=lm.vocab, image=e16.cfg.vision.image)
             kw = dict(images=imgs, use_dd_unk=True, use_dd=nb == 3, cd_alpha=1.0, cd_beta=0.1, temperature=0.5, max_new_tokens=NEW, seed=1)
             if "--trace" in args:
@@ -141,28 +175,37 @@ def main():
                         step_ms(e8, ids, kw, True), step_ms(e16, ids, kw, False)
                     torch.cuda.synchronize()
                 continue
-            for _ in range(2):                                    # warm-up: forms measured, steps captured
-                step_ms(e16, ids, kw, False), step_ms(e8, ids, kw, True)
-            t16, t8 = [], []
-            for _ in range(REPS):                                 # alternating legs
-                t16.append(step_ms(e16, ids, kw, False))
-                t8.append(step_ms(e8, ids, kw, True))
-            dt = ops._MODEL_DT[e16.dtype]
-            rec = dict(shape=name, layers=lm.n_layers, dtype="bf16", rows=rows, questions=Q, new_tokens=NEW, reps=REPS,
-                       w16_ms=round(statistics.median(t16), 4), w8_ms=round(statistics.median(t8), 4),
-                       w16_ms_all=[round(v, 4) for v in t16], w8_ms_all=[round(v, 4) for v in t8],
-                       w16_layer_form=ops._form_choice.get(("layer", rows, lm.d, 0, dt)), w8_layer_form=ops._form_choice.get(("layer", rows, lm.d, 8, dt)),
-                       w16_stream_gb=round(stream_bytes(e16, False, rows) / 1e9, 3), w8_stream_gb=round(stream_bytes(e8, True, rows) / 1e9, 3),
-                       w8_forms={",".join(map(str, k)): v for k, v in ops._form_choice.items() if str(k[0]).endswith("8") and k[0] != "layer"} if rows > 16 else None)
-            rec["speedup"] = round(rec["w16_ms"] / rec["w8_ms"], 3)
-            if Q == 1:
-                rec["w16_tok_s"], rec["w8_tok_s"] = round(1e3 / rec["w16_ms"], 1), round(1e3 / rec["w8_ms"], 1)
-            line = json.dumps(rec)
-            print(line, flush=True)
-            if out:
-                os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-                with open(out, "a") as f:
-                    f.write(line + "\n")
+            for mode in modes:
+                inv = mode == "invariant"
+                mkw = dict(kw, cd_greedy=True) if inv else kw         # the mode is what the drivers select for deterministic decodes
+                with ops.batch_invariant(inv):
+                    for _ in range(2):                                # warm-up: forms measured, steps captured
+                        step_ms(e16, ids, mkw, False), step_ms(e8, ids, mkw, True)
+                    t16, t8 = [], []
+                    for _ in range(REPS):                             # alternating legs
+                        t16.append(step_ms(e16, ids, mkw, False))
+                        t8.append(step_ms(e8, ids, mkw, True))
+                dt = ops._MODEL_DT[e16.dtype]
+                bucket = ops._form_key("linear8", rows, 0, 0, dt)[1]
+                kinds8 = tuple(k + (ops.INVARIANT_KIND_SUFFIX if inv else "") for k in ("linear8", "to_norm8", "swiglu8"))
+                rec = dict(shape=name, layers=lm.n_layers, dtype="bf16", mode=mode, rows=rows, questions=Q, new_tokens=NEW, reps=REPS,
+                           w16_ms=round(statistics.median(t16), 4), w8_ms=round(statistics.median(t8), 4),
+                           w16_ms_all=[round(v, 4) for v in t16], w8_ms_all=[round(v, 4) for v in t8],
+                           w16_layer_form=None if inv else ops._form_choice.get(("layer", rows, lm.d, 0, dt)),
+                           w8_layer_form=None if inv else ops._form_choice.get(("layer", rows, lm.d, 8, dt)),
+                           w16_stream_gb=round(stream_bytes(e16, False, rows) / 1e9, 3), w8_stream_gb=round(stream_bytes(e8, True, rows) / 1e9, 3),
+                           w8_forms={",".join(map(str, k)): v for k, v in ops._form_choice.items() if k[0] in kinds8 and k[1] == bucket})
+                rec["speedup"] = round(rec["w16_ms"] / rec["w8_ms"], 3)
+                rec["w16_spread_ms"] = round(max(t16) - min(t16), 4)
+                rec["w8_slower_beyond_spread"] = bool(rec["w8_ms"] - rec["w16_ms"] > rec["w16_spread_ms"])
+                if Q == 1:
+                    rec["w16_tok_s"], rec["w8_tok_s"] = round(1e3 / rec["w16_ms"], 1), round(1e3 / rec["w8_ms"], 1)
+                line = json.dumps(rec)
+                print(line, flush=True)
+                if out:
+                    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+                    with open(out, "a") as f:
+                        f.write(line + "\n")
         del e16, e8
         torch.cuda.empty_cache()
 
