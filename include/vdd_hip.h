@@ -375,6 +375,27 @@ int vdd_decode_attention_grouped(const void* q, const void* k_cache, const void*
                                  int64_t prefix_stride, int prefix_tmax, int max_prefix_len, int max_own_len,
                                  int prefix_chunks_per_item, float scale, int dtype, void* hip_stream);
 
+/* Batch-invariant mode with shared prefixes.  The output of (row, head) is a function of q[row, head], the K / V of the row's
+ * context keys in key order, the row's len and its prefix_len - NOT of M, the row's place in the call, the other rows or groups, a
+ * group's size / index / order, slot numbers, max_*_len, n_items or the workspace size.  row_mode[i] (int32) names the row's kind:
+ *   1 = shared: listed in exactly one group (a group of ONE row included); its prefix is attended by the MFMA prefix pass of
+ *       vdd_decode_attention_grouped with a chunk walk derived from (head, item index, prefix_len) alone, its own keys in split-KV
+ *       chunks at prefix_len + 64 c whatever their number, and the partials merge in one order: prefix items ascending, then own
+ *       chunks ascending;
+ *   0 = per row: in no group; the whole context in chunks at 64 c, prefix keys from k_prefix / v_prefix - bit-identical to
+ *       vdd_decode_attention on the same pools, wherever prefix_len cuts the context.
+ * prefix_chunks_per_item is part of the arithmetic (it places the cuts of the prefix's online softmax): one value for every call
+ * whose results are to be compared.  max_prefix_len / max_own_len bound prefix_len / len - prefix_len of the shared rows,
+ * max_row_len the len of the per-row rows (0: there are none).  Refused before any launch (VDD_ERR_INVALID_ARG): a null argument,
+ * D != 128, prefix_chunks_per_item < 1, and with n_items > 0 a null prefix_frag or prefix_tmax % 64 != 0.
+ * Workspace: vdd_decode_attention_workspace_bytes(M, H, D, max(round_up(max_prefix_len, 64) + round_up(max_own_len, 64), max_row_len)). */
+int vdd_decode_attention_shared_invariant(const void* q, const void* k_cache, const void* v_cache, const void* k_prefix, const void* v_prefix,
+                                          const void* prefix_frag, const int32_t* rows, const int32_t* row_mode, const int32_t* groups,
+                                          const int32_t* group_rows, const int32_t* items, int n_items, void* out, void* workspace, int M,
+                                          int H, int Hkv, int D, int64_t slot_stride, int t_max, int64_t prefix_stride, int prefix_tmax,
+                                          int max_prefix_len, int max_own_len, int max_row_len, int prefix_chunks_per_item, float scale,
+                                          int dtype, void* hip_stream);
+
 /* Fragment-major copy of the prefix pool for the MFMA prefix pass: prefix_frag[slot][kv_head][chunk] = one 32-KiB block per
  * 64-key chunk (t_max % 64 == 0; twice the bytes and slot stride of k_prefix), 16 K fragments then 16 V^T fragments, each
  * the 1-KiB lane-linear image of one 16x16x32 MFMA operand; keys >= prefix_len_of_slot[slot] are zero-filled.  Built once

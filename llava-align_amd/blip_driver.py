@@ -26,7 +26,7 @@ import torch
 from . import calibrate as C
 from . import shard
 from .blip_frontend import InstructBlipFrontEnd
-from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, load_kw, add_script_args, answer_text, chunk_of, distinct, eos_set, finish_distributed, load_distinct_images,
+from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, load_kw, mode_kw, add_script_args, answer_text, chunk_of, distinct, eos_set, finish_distributed, load_distinct_images,
                             pope_scores_for, read_questions, to_all_rows, write_jsonl)
 from .engine import VddLlavaEngine
 from .vcd_add_noise import add_diffusion_noise
@@ -47,7 +47,7 @@ def run_blip_pope(engine: VddLlavaEngine, front: InstructBlipFrontEnd, questions
                   repetition_penalty: float = 1.0,
                   max_length: int = 256, min_length: int = 1, eos_token_id=2, pad_token_id: Optional[int] = 2,
                   model_id: str = "instruct_blip", rank: Optional[int] = None, world: Optional[int] = None,
-                  batch_invariant: Optional[bool] = None, **generate_kw) -> dict:
+                  batch_invariant: Optional[bool] = None, invariant_shared_prefix: bool = False, **generate_kw) -> dict:
     """questions: POPE json lines (question_id, image, text[, label]).  Defaults are the reference driver's: top_p 1, temperature 1,
     top_k 50 (LAVIS never passes top_k, so HF's GenerationConfig default warps every sampled step: blip2_vicuna_instruct.py:390-410),
     repetition_penalty 1, max_length 256, min_length 1, cd_alpha left at the sampler's default (None -> 0.5), noise_step 500.
@@ -55,7 +55,7 @@ def run_blip_pope(engine: VddLlavaEngine, front: InstructBlipFrontEnd, questions
     its chunk of whole images (shard.ShardPlan; BASELINE config #5 runs on 4 GPUs), ONE collective gathers the results, rank 0 writes
     the file, every rank returns the full result.  Returns {"answers": [...], "scores": {...}}; the JSONL has the reference's
     fields (question_id, prompt, text, model_id, image, naive, noise, zeros, metadata; blip_calibrate.py:100-109)."""
-    run = ShardedRun(questions, rank, world, generate_kw, batch_invariant)      # (invariant mode: the LM side; the EVA-ViT / Q-Former front-end is per image / per question)
+    run = ShardedRun(questions, rank, world, generate_kw, batch_invariant, invariant_shared_prefix)      # (invariant mode: the LM side; the EVA-ViT / Q-Former front-end is per image / per question)
     decode_token = lambda t: decode([t])
     embed = engine.w.t["embed"]
     base_kw = dict(do_sample=True, top_p=top_p, top_k=top_k, temperature=temperature, num_beams=1, repetition_penalty=repetition_penalty,
@@ -160,7 +160,7 @@ def main(argv=None):
                         lambda p: bert(p, truncation=True, max_length=a.max_txt_len).input_ids,
                         lambda ids: llm_tok.decode(ids, skip_special_tokens=True), lambda name: blip_image_eval(os.path.join(a.image_folder, name), size),
                         answers_path=os.path.expanduser(a.answers_file), batch_questions=a.batch, use_cd=a.use_cd, noise_step=a.noise_step, cd_beta=a.cd_beta,
-                        top_p=a.top_p, rank=rank, world=world, seed=a.seed)
+                        top_p=a.top_p, rank=rank, world=world, seed=a.seed, **mode_kw(a))
     if rank == 0:
         nan = {k: v["nan_rows"] for k, v in res["scores"].items() if isinstance(v, dict) and v.get("nan_rows")}
         print(json.dumps({"scores": res["scores"], "n_answers": len(res["answers"]), "rows_whose_calibrated_vector_is_nan": nan}, indent=1))

@@ -7,6 +7,8 @@
 //   vdd_decode_attention_paged             the same over the paged own-KV pool: decode_attn_paged_kernel + combine
 //   vdd_decode_attention_grouped           shared prefixes once per group on the matrix cores (decode_attn_prefix_mfma_kernel), then
 //                                          the own keys: decode_attn_own_merge_kernel (<= 256 own keys) or decode_attn_kernel + combine
+//   vdd_decode_attention_shared_invariant  batch-invariant mode with shared prefixes: the MFMA prefix pass with a batch-free chunk walk, then
+//                                          decode_attn_mixed_kernel (per row: own chunks behind the prefix, or whole-context chunks) + combine
 //   vdd_decode_attention_fused             few rows: RoPE + KV-cache write + whole-context attention + merge in ONE kernel
 //   vdd_decode_attention_fused_split       ... with the old keys split 2 or 4 ways across blocks (ticket merge)
 //   vdd_prefix_fragments                   fragment-major copy of a prefix's K / V for the MFMA prefix pass (once per generate)
@@ -286,6 +288,56 @@ __global__ void __launch_bounds__(256) decode_attn_combine_kernel(const float* _
     store_out_pair(out + ((size_t)row * H + head) * D, lane, a0, a1, L);
 }
 
+// ------------------------------------------------------------------ batch-invariant mode with shared prefixes
+// vdd_decode_attention_shared_invariant: what a (row, head) computes is a function of its q, its keys in key order, its len and its
+// prefix length alone.  mode[row] = 1 (shared: the prefix partials come from the MFMA pass, whose chunk walk knows only head, item and
+// plen; the own keys are cut at plen + 64 c) or 0 (per row: the whole context cut at 64 c, prefix keys from the row-major pool - the
+// arithmetic of decode_attn_kernel, bit for bit).  Records of a row: shared = [0, npre) prefix items, then own chunks; per row = chunks from 0.
+template <int D>
+__global__ void __launch_bounds__(256) decode_attn_mixed_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
+                                                                const uint16_t* __restrict__ vc, const uint16_t* __restrict__ kpre,
+                                                                const uint16_t* __restrict__ vpre, const AttnRow* __restrict__ rows,
+                                                                const int* __restrict__ mode, float* __restrict__ ws, int H, int Hkv,
+                                                                long long slot_stride, int t_max, long long pre_stride, int pre_tmax,
+                                                                float scale, int nchunk, int npre, int nown, int nrow) {
+    const int shared = mode[blockIdx.y] != 0;
+    if ((int)blockIdx.z >= (shared ? nown : nrow)) return;        // records past the row's kind would lie outside its nchunk
+    decode_attn_chunk<D>(q, OwnContiguous<D>{kc, vc, slot_stride, t_max}, kpre, vpre, rows, ws, H, Hkv, pre_stride, pre_tmax, scale, nchunk,
+                         shared, shared ? npre : 0);
+}
+
+// decode_attn_combine_kernel with the row's kind from `mode`: prefix items ascending, then own chunks ascending; a per-row row has no
+// prefix items and its chunks start at record 0 (the same sums in the same order as the combine of vdd_decode_attention)
+template <int D>
+__global__ void __launch_bounds__(256) decode_attn_combine_mixed_kernel(const float* __restrict__ ws, const AttnRow* __restrict__ rows,
+                                                                        const int* __restrict__ mode, uint16_t* __restrict__ out, int H,
+                                                                        int nchunk, int npre, int pre_keys) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int head = blockIdx.x * 4 + wave, row = blockIdx.y;
+    if (head >= H) return;
+    const AttnRow ar = rows[row];
+    const bool shared = mode[row] != 0;
+    const int used_pre = shared ? (ar.plen + pre_keys - 1) / pre_keys : 0;
+    const int own_base = shared ? npre : 0;
+    const int own_len = shared ? ar.len - ar.plen : ar.len;
+    const int used_own = min(nchunk - own_base, (own_len + ATT_CH - 1) / ATT_CH);
+    const float* base = ws + ((size_t)row * H + head) * nchunk * ATT_PS;
+    float M = -INFINITY;
+    for (int c = 0; c < used_pre; ++c) M = fmaxf(M, base[c * ATT_PS + D]);
+    for (int c = 0; c < used_own; ++c) M = fmaxf(M, base[(own_base + c) * ATT_PS + D]);
+    float L = 0.f, a0 = 0.f, a1 = 0.f;
+    auto add = [&](int c) {
+        const float* p = base + c * ATT_PS;
+        const float w = __expf(p[D] - M);
+        L += w * p[D + 1];
+        const float2 v = *reinterpret_cast<const float2*>(p + 2 * lane);
+        a0 += w * v.x; a1 += w * v.y;
+    };
+    for (int c = 0; c < used_pre; ++c) add(c);
+    for (int c = 0; c < used_own; ++c) add(own_base + c);
+    store_out_pair(out + ((size_t)row * H + head) * D, lane, a0, a1, L);
+}
+
 // ------------------------------------------------------------------ small-M fused decode attention
 // For a handful of rows (the reference's own operating point: ONE question = 2-3 branch rows) the step is a chain of
 // latency-bound launches, so RoPE, the KV-cache write, the whole-context attention and the merge run as ONE kernel:
@@ -490,7 +542,9 @@ __global__ void __launch_bounds__(256) prefix_fragments_kernel(const uint16_t* _
 
 // waves-per-SIMD hint 4: left alone the compiler hoists all 16 K (then V) fragment loads of a chunk and lands at 140
 // registers = 3 waves per SIMD; capped at 128 the pass is 10 % faster (tools/attn_probe.py: 314 -> 274 us per layer).
-template <int D>
+// INVARIANT (vdd_decode_attention_shared_invariant): the chunk walk of an item may know the head, the item's index inside the prefix and
+// plen, never the group, the slice or the slot - a row's partial must not change with its neighbours.
+template <int D, bool INVARIANT = false>
 __global__ void __launch_bounds__(256, 2) decode_attn_prefix_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ frag,
                                                                       const GroupDesc* __restrict__ groups,
                                                                       const int* __restrict__ group_rows, const int4* __restrict__ items,
@@ -525,7 +579,7 @@ __global__ void __launch_bounds__(256, 2) decode_attn_prefix_mfma_kernel(const u
     // Chunks in a ROTATED order (the online softmax does not care): every (group, head) stream starts at t = 0 of a region that
     // is a multiple of 32 KiB away from the others', so waves walking in step would all sit on the same HBM channels
     const int nch_i = (k1 - kbeg + ATT_CH - 1) / ATT_CH;
-    const int rot = (int)((unsigned)(head * 5 + item.x * 3 + r0) % (unsigned)nch_i);
+    const int rot = (int)((unsigned)(INVARIANT ? head * 5 + part * 3 : head * 5 + item.x * 3 + r0) % (unsigned)nch_i);
     for (int ci = 0; ci < nch_i; ++ci) {
         const int cc = ci + rot < nch_i ? ci + rot : ci + rot - nch_i;
         const int k0 = kbeg + cc * ATT_CH;
@@ -725,6 +779,35 @@ VDD_HIDDEN int VDD_IMPL(vdd_decode_attention_grouped)(const void* q, const void*
                        (const AttnRow*)rows, (float*)workspace, H, Hkv, (long long)slot_stride, t_max, (long long)prefix_stride,
                        prefix_tmax, scale, nchunk, 1, npre);
     launch_combine(workspace, rows, out, M, H, nchunk, npre, pre_keys, st);
+    return ok(hipSuccess);
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_decode_attention_shared_invariant)(const void* q, const void* k_cache, const void* v_cache, const void* k_prefix,
+                                          const void* v_prefix, const void* prefix_frag, const int32_t* rows, const int32_t* row_mode,
+                                          const int32_t* groups, const int32_t* group_rows, const int32_t* items, int n_items, void* out,
+                                          void* workspace, int M, int H, int Hkv, int D, int64_t slot_stride, int t_max,
+                                          int64_t prefix_stride, int prefix_tmax, int max_prefix_len, int max_own_len, int max_row_len,
+                                          int prefix_chunks_per_item, float scale, void* stream) {
+    if (M <= 0) return VDD_OK;
+    if (!q || !k_cache || !v_cache || !k_prefix || !v_prefix || !rows || !row_mode || !groups || !group_rows || !items || !out || !workspace ||
+        D != 128 || Hkv <= 0 || H % Hkv != 0 || max_prefix_len < 0 || max_own_len < 0 || max_row_len < 0 || max_own_len + max_row_len <= 0 ||
+        n_items < 0 || n_items > 65535 || prefix_chunks_per_item < 1) return VDD_ERR_INVALID_ARG;
+    if (n_items > 0 && (prefix_frag == nullptr || prefix_tmax % ATT_CH != 0)) return VDD_ERR_INVALID_ARG;
+    const int sub = prefix_chunks_per_item, pre_keys = ATT_CH * sub;
+    const int npre = (max_prefix_len + pre_keys - 1) / pre_keys, nown = (max_own_len + ATT_CH - 1) / ATT_CH, nrow = (max_row_len + ATT_CH - 1) / ATT_CH;
+    const int nchunk = npre + nown > nrow ? npre + nown : nrow;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_items > 0 && npre > 0) {
+        hipLaunchKernelGGL((decode_attn_prefix_mfma_kernel<128, true>), dim3((H + 3) / 4, n_items), dim3(256), 0, st,
+                           (const uint16_t*)q, (const uint16_t*)prefix_frag, (const GroupDesc*)groups, group_rows,
+                           (const int4*)items, (float*)workspace, H, Hkv, (long long)prefix_stride, prefix_tmax, scale, nchunk, sub);
+    }
+    hipLaunchKernelGGL(decode_attn_mixed_kernel<128>, dim3((H + 3) / 4, M, nown > nrow ? nown : nrow), dim3(256), 0, st, (const uint16_t*)q,
+                       (const uint16_t*)k_cache, (const uint16_t*)v_cache, (const uint16_t*)k_prefix, (const uint16_t*)v_prefix,
+                       (const AttnRow*)rows, row_mode, (float*)workspace, H, Hkv, (long long)slot_stride, t_max, (long long)prefix_stride,
+                       prefix_tmax, scale, nchunk, npre, nown, nrow);
+    hipLaunchKernelGGL(decode_attn_combine_mixed_kernel<128>, dim3((H + 3) / 4, M), dim3(256), 0, st, (const float*)workspace,
+                       (const AttnRow*)rows, row_mode, (uint16_t*)out, H, nchunk, npre, pre_keys);
     return ok(hipSuccess);
 }
 

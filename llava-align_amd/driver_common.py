@@ -2,7 +2,7 @@
 two small classes; what makes each driver worth having - which passes a batch runs, which priors, what its JSONL record looks like -
 stays in its `run_*`, which reads top to bottom and calls these.
 
-  ShardedRun              image-sorted order, ShardPlan, this rank's questions, the rank's seed offset, batch-invariant mode
+  ShardedRun              image-sorted order, ShardPlan, this rank's questions, the rank's seed offset, batch-invariant mode (+ its shared-prefix form)
   ResultRows              a rank's per-question results in the layout of the one result gather (shard.gather_results), with or without top lists
   distinct / to_all_rows  every DISTINCT prompt runs once; its step-0 top list goes back to all the rows that asked it
   load_distinct_images    one tensor OBJECT per image name (the engine shares ViT features and prefix KV by tensor identity)
@@ -49,7 +49,8 @@ class ShardedRun:
     adjacent, split over the ranks by whole images (shard.ShardPlan; rank / world default to the initialised torch.distributed group, else
     one rank), an explicit `seed` offset by the rank, and whether the decode runs in batch-invariant mode (shard.resolve_batch_invariant)."""
 
-    def __init__(self, questions: Sequence[dict], rank: Optional[int], world: Optional[int], generate_kw: dict, batch_invariant: Optional[bool]):
+    def __init__(self, questions: Sequence[dict], rank: Optional[int], world: Optional[int], generate_kw: dict, batch_invariant: Optional[bool],
+                 invariant_shared_prefix: bool = False):
         order = sorted(range(len(questions)), key=lambda i: (questions[i]["image"], i))
         self.questions = questions
         self.plan = ShardPlan([questions[i]["image"] for i in order], rank, world)
@@ -59,9 +60,12 @@ class ShardedRun:
             generate_kw = dict(generate_kw, seed=int(generate_kw["seed"]) + self.rank)
         self.generate_kw = generate_kw
         self.invariant = resolve_batch_invariant(batch_invariant, self.world, generate_kw)
+        # the mode's shared-prefix form (ops.INVARIANT_SHARED_PREFIX: image prefixes once per image, still batch-invariant): opt-in, and only
+        # where the run is in the mode at all
+        self.shared_prefix = bool(invariant_shared_prefix) and self.invariant
 
     def mode(self):
-        return ops.batch_invariant() if self.invariant else contextlib.nullcontext()
+        return ops.batch_invariant(shared_prefix=self.shared_prefix) if self.invariant else contextlib.nullcontext()
 
     def batches(self, n: int):
         for b0 in range(0, len(self.mine), n):
@@ -217,6 +221,9 @@ def add_common_args(ap, help: Optional[dict] = None, dtype: str = "float16", **d
         ap.add_argument(flag, type=typ, help=(help or {}).get(dest), **(dict(required=True) if default is REQUIRED else dict(default=default)))
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default=dtype, help="model dtype (the reference loads LLaVA / Vicuna in fp16, builder.py:40)")
     ap.add_argument("--load-8bit", action="store_true", default=argparse.SUPPRESS, help="e4m3 weight storage for the few-row decode step (builder.py:26-31 load_8bit; VddLlavaEngine(load_8bit=True))")
+    ap.add_argument("--invariant-shared-prefix", action="store_true", default=argparse.SUPPRESS,
+                    help="batch-invariant runs only: read an image prefix once per image (ops.INVARIANT_SHARED_PREFIX); still the same answers at any batch "
+                         "size and rank count, but not the bits of a run without the option; open-ended lists (generate_list) refuse it")
     if defaults:
         raise TypeError(f"not common options: {sorted(defaults)}")
 
@@ -224,6 +231,11 @@ def add_common_args(ap, help: Optional[dict] = None, dtype: str = "float16", **d
 def load_kw(a) -> dict:
     """The loader / engine keywords the common options select: `load_8bit=True` after --load-8bit, nothing otherwise."""
     return dict(load_8bit=True) if getattr(a, "load_8bit", False) else {}
+
+
+def mode_kw(a) -> dict:
+    """The run keyword --invariant-shared-prefix selects (`invariant_shared_prefix=True`), nothing otherwise: off by default."""
+    return dict(invariant_shared_prefix=True) if getattr(a, "invariant_shared_prefix", False) else {}
 
 
 def add_script_args(ap, conv_mode: str = "llava_v1") -> None:

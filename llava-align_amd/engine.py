@@ -381,15 +381,18 @@ class KVCache:
             and converts the scratch into `pfrag[i]` before the next layer overwrites it.  Round 3 kept both forms for every layer:
             129 slots x 4 x 168 MB = 87 GB of the 189 GB peak of a 768-question batch, half of it read once;
     `pre`   (frag_only=False: few rows in flight / nothing worth grouping - the decode kernels read row-major prefixes) per-layer
-            row-major pools [n_pre, n_kv_heads, t_pre, head_dim], token t at index t, and no fragment image at all.
+            row-major pools [n_pre, n_kv_heads, t_pre, head_dim], token t at index t, and no fragment image at all;
+    `pre` + `frag` (with_frag=True: the shared-prefix form of the batch-invariant mode, ops.INVARIANT_SHARED_PREFIX) the per-layer row-major
+            pools AND a per-layer fragment image beside them: rows behind a canonical prefix (image / declared embeds_prefix) attend the
+            image, every other row its row-major prefix - one prefix pool more than `pre` alone.
     Paged form (n_pages > 0, generate_list(paged_kv=True); row-major prefixes): the decode steps keep their own tokens in page pools
     `pk` / `pv` [n_pages, n_kv_heads, PAGE, head_dim] behind `page_table` (int32 [n_own, max_pages], indexed by own-slot id, static:
     the captured steps read it, the host rewrites it between replays); `own` shrinks to a staging area of t_own = the longest
     suffix, which the admission prefill writes and vdd_kv_pages_scatter empties into the pages."""
 
     def __init__(self, lm: LMConfig, n_pre: int, t_pre: int, n_own: int, t_own: int, device, dtype=torch.bfloat16, frag_only: bool = False,
-                 n_pages: int = 0, max_pages: int = 0):
-        self.dtype, self.frag_only = dtype, frag_only
+                 n_pages: int = 0, max_pages: int = 0, with_frag: bool = False):
+        self.dtype, self.frag_only, self.with_frag = dtype, frag_only, bool(with_frag) and not frag_only
         self.n_pre, self.t_pre, self.n_own, self.t_own = n_pre, t_pre, n_own, t_own
         self.n_pages, self.max_pages = n_pages, max_pages
         self.pk = self.pv = self.page_table = None
@@ -405,18 +408,18 @@ class KVCache:
             self.pfrag = mk(n_pre, 2 * t_pre)
         else:
             self.kp, self.vp = mk(n_pre, t_pre), mk(n_pre, t_pre)
-            self.pfrag = [None] * lm.n_layers
+            self.pfrag = mk(n_pre, 2 * t_pre) if self.with_frag else [None] * lm.n_layers
         self.ko, self.vo = mk(n_own, t_own), mk(n_own, t_own)
 
     @staticmethod
-    def bytes_needed(lm: LMConfig, n_pre, t_pre, n_own, t_own, dtype, frag_only, n_pages=0) -> int:
+    def bytes_needed(lm: LMConfig, n_pre, t_pre, n_own, t_own, dtype, frag_only, n_pages=0, with_frag=False) -> int:
         per = lm.n_kv_heads * lm.head_dim * (2 if dtype in (torch.bfloat16, torch.float16) else 4)
         pre = max(n_pre, 1) * t_pre * per * 2
         return (lm.n_layers * (max(n_own, 1) * t_own + n_pages * PAGE) * per * 2
-                + (lm.n_layers * pre + pre if frag_only else lm.n_layers * pre))
+                + (lm.n_layers * pre + pre if frag_only else lm.n_layers * pre * (2 if with_frag else 1)))
 
-    def fits(self, n_pre, t_pre, n_own, t_own, frag_only, n_pages=0, max_pages=0):
-        return (frag_only == self.frag_only and n_pre <= self.n_pre and t_pre <= self.t_pre and n_own <= self.n_own and t_own <= self.t_own
+    def fits(self, n_pre, t_pre, n_own, t_own, frag_only, n_pages=0, max_pages=0, with_frag=False):
+        return (frag_only == self.frag_only and bool(with_frag) == self.with_frag and n_pre <= self.n_pre and t_pre <= self.t_pre and n_own <= self.n_own and t_own <= self.t_own
                 and bool(n_pages) == bool(self.n_pages) and n_pages <= self.n_pages and max_pages <= self.max_pages)
 
     @property
@@ -542,7 +545,8 @@ class LanguageModel:
         sequence alone, and nothing past the KV write in a pass whose hidden states feed no logits (the reference runs all
         positions through everything, llava_llama.py:88-103).
         frag_plen (int32 [n_prefix slots], with kv.frag_only): after a layer's passes its row-major prefix K/V - the scratch every
-        layer shares - is converted into that layer's fragment image for the decode steps."""
+        layer shares - is converted into that layer's fragment image for the decode steps.  With kv.with_frag the image is built beside
+        the layer's own row-major pool, for the slots with frag_plen > 0 (the canonical ones)."""
         c, t = self.cfg, self.w.t
         H, Hkv, D = c.n_heads, c.n_kv_heads, c.head_dim
         state = [dict(resid=p["x"], delta=None, done=False) for p in passes]
@@ -674,6 +678,14 @@ class LanguageModel:
                 # a few rows (one question in flight): RoPE + KV write + attention + merge in one launch
                 att = ops.decode_attention_fused(qkv, pos, cpos, slot, self.cs, kv.ko[i], kv.vo[i], attn_rows, H, Hkv, D,
                                                  k_prefix=kv.kp[i], v_prefix=kv.vp[i])
+            elif grouping is not None and grouping.get("row_mode") is not None:
+                # batch-invariant mode, shared-prefix form: canonical prefixes once per image (MFMA, batch-free chunk walk), every
+                # other row exactly as decode_attention below
+                q = ops.rope_kv_write(qkv, pos, slot, self.cs, kv.ko[i], kv.vo[i], H, Hkv, D, cpos=cpos)
+                att = ops.decode_attention_shared_invariant(q, kv.ko[i], kv.vo[i], kv.kp[i], kv.vp[i], attn_rows, grouping["row_mode"],
+                                                            grouping["groups"], grouping["group_rows"], grouping["items"], grouping["n_items"],
+                                                            H, Hkv, D, kv.t_pre, kv.t_own, grouping["max_row_len"], kv.pfrag[i],
+                                                            workspace=grouping["workspace"], chunks_per_item=grouping["cpi"])
             elif grouping is not None:    # rows sharing a prompt prefix attend it once per group (MFMA), own tokens per row
                 q = ops.rope_kv_write(qkv, pos, slot, self.cs, kv.ko[i], kv.vo[i], H, Hkv, D, cpos=cpos)
                 att = ops.decode_attention_grouped(q, kv.ko[i], kv.vo[i], kv.kp[i], kv.vp[i], attn_rows, grouping["groups"],
@@ -825,6 +837,10 @@ class _DecodeRunner:
                                  n_groups=tail["n_groups"], items=torch.zeros(max(1, tail["n_items"]), 4, **i32), n_items=tail["n_items"],
                                  cpi=tail.get("cpi", 1),
                                  workspace=self.workspace)
+            if tail.get("inv_shared"):
+                # the shared-prefix form of the batch-invariant mode: the row kinds (1 = behind a canonical prefix, in a group; 0 = per row)
+                # beside the group tables; a per-row row may be as long as the pools allow
+                self.grouping.update(row_mode=torch.zeros(R, **i32), max_row_len=kv.t_pre + kv.t_own if tail["inv_shared"] < R else 0)
 
     def set_processor_inputs(self, eos_min=None, prompt_tail=None, prompt_ids=None):
         """Per-call data of the processor stage into the runner's static buffers (a captured step points at them)."""
@@ -878,11 +894,15 @@ class _DecodeRunner:
         self.step_idx.fill_(0)
         self.ctr.fill_(ctr0)
 
-    def load(self, pos, cpos, slot, rows):
+    def load(self, pos, cpos, slot, rows, row_mode=None):
         dev = self.pos.device
         if self.grouping is not None:
-            groups, members = group_rows_by_prefix(rows)
-            items = ops.prefix_work_items(groups, self.grouping["cpi"])
+            if self.grouping.get("row_mode") is not None:
+                groups, members, items = ops.invariant_prefix_work(rows, row_mode, self.grouping["cpi"])
+                self.grouping["row_mode"].copy_(h2d_int32(dev, row_mode)[0])
+            else:
+                groups, members = group_rows_by_prefix(rows)
+                items = ops.prefix_work_items(groups, self.grouping["cpi"])
             assert len(groups) == self.grouping["n_groups"] and len(items) == self.grouping["n_items"]
             p_, c_, s_, r_, g_, i_, m_ = h2d_int32(dev, pos, cpos, slot, rows, groups, items, members)
             self.grouping["groups"].copy_(g_)
@@ -1104,16 +1124,17 @@ class VddLlavaEngine:
         self.call_log: Optional[list] = None
 
     # -- plumbing ---------------------------------------------------------------------------
-    def kv(self, n_pre, t_pre, n_own, t_own, frag_only=False, n_pages=0, max_pages=0):
-        """The KV pools for a call, one cache per pool form (KVCache.frag_only, or "paged" for the paged own-KV form of generate_list): a
+    def kv(self, n_pre, t_pre, n_own, t_own, frag_only=False, n_pages=0, max_pages=0, with_frag=False):
+        """The KV pools for a call, one cache per pool form (KVCache.frag_only, "paged" for the paged own-KV form of generate_list, or "shared" for
+        the row-major + fragment form of the batch-invariant mode's shared-prefix decode): a
         driver alternates calls that group their decode rows (the image questions) with calls that do not (a handful of rows), and each
         keeps its pools - and the decode graphs captured over them - across calls; a cache only grows."""
         # prefix slots are whole 64-key chunks (the fragment image); own slots only need whole 16-key groups: 92 own tokens take
         # 96 rows, not 128 (a quarter of the own pool, 26 GB at 768 questions)
         t_pre, t_own = (max(t_pre, 64) + 63) // 64 * 64, (max(t_own, 64) + 15) // 16 * 16
-        form = "paged" if n_pages else frag_only
+        form = "paged" if n_pages else ("shared" if with_frag else frag_only)
         cur = self._kvs.get(form)
-        if cur is None or not cur.fits(n_pre, t_pre, n_own, t_own, frag_only, n_pages, max_pages):
+        if cur is None or not cur.fits(n_pre, t_pre, n_own, t_own, frag_only, n_pages, max_pages, with_frag):
             self._kvs.pop(form, None)
             self._drop_graphs(cur)
             grow = lambda a, b: max(a, b)
@@ -1123,7 +1144,7 @@ class VddLlavaEngine:
             if self._kv is cur:
                 self._kv = None
             del cur
-            need = KVCache.bytes_needed(self.cfg.lm, n_pre, t_pre, n_own, t_own, self.dtype, frag_only, n_pages)
+            need = KVCache.bytes_needed(self.cfg.lm, n_pre, t_pre, n_own, t_own, self.dtype, frag_only, n_pages, with_frag)
             for other_form in [f for f in self._kvs if f != form]:
                 if self.device.type != "cuda":
                     break
@@ -1138,7 +1159,7 @@ class VddLlavaEngine:
                     gc.collect()
                     torch.cuda.empty_cache()
             self._kvs[form] = KVCache(self.cfg.lm, n_pre, t_pre, n_own, t_own, self.device, self.dtype, frag_only=frag_only, n_pages=n_pages,
-                                      max_pages=max_pages)
+                                      max_pages=max_pages, with_frag=with_frag)
         self._kv = self._kvs[form]
         return self._kv
 
@@ -1258,7 +1279,12 @@ class VddLlavaEngine:
 
         streamer (HF BaseStreamer: llava/serve/cli.py [ext] passes a TextStreamer): `put(prompt ids)` as HF's generate() does before
         sampling, `put(next token)` after every step (vcd_sample.py:264-265: one device -> host copy per step) and `end()` at the
-        end (:299-300).  One question per call, as HF's own streamers require."""
+        end (:299-300).  One question per call, as HF's own streamers require.
+
+        In batch-invariant mode with ops.INVARIANT_SHARED_PREFIX (`with ops.batch_invariant(shared_prefix=True):`) the decode rows behind a
+        canonical prefix slot (_plan: image prefix, declared embeds_prefix) attend it through ops.decode_attention_shared_invariant, once
+        per image and still batch-invariant; stats["n_groups"] > 0 and stats["shared_rows"] then count the groups and their rows.  Row
+        retirement stays off while groups exist, in that form as in the tuned one."""
         dev, lm = self.device, self.cfg.lm
         events = None
         if self.call_log is not None and dev.type == "cuda":
@@ -1363,7 +1389,15 @@ class VddLlavaEngine:
         sel = [b_ * Q + q for b_ in keep for q in range(Q)]
         dec_rows = [[seg[i]["slot"], seg[i]["pos0"] + seg[i]["T"] + 1, seg[i]["pslot"], seg[i]["plen"]] for i in sel]
         grp, _members = group_rows_by_prefix(dec_rows) if (self.group_attention and not ops.GEMM_BATCH_INVARIANT) else ([], [])
-        if grp and (not grouping_pays(grp, dec_rows) or (len(dec_rows) <= ops.FUSED_ATTN_MAX_M and lm.head_dim == 128)):
+        # batch-invariant mode with ops.INVARIANT_SHARED_PREFIX: the rows behind a CANONICAL prefix slot (_plan: image prefix, declared
+        # embeds_prefix - a cut that is a property of the prompt) are grouped by it, a row whose image nobody else asks about as a group of
+        # one; whether a batch is worth grouping is never asked (grouping_pays and the 16-row rule look at the batch)
+        dec_mode, inv_items = None, []
+        if self.group_attention and ops.invariant_shared_prefix() and lm.head_dim == 128:
+            dec_mode = [int(r[3] > 0 and bool(plan["prefix"][r[2]].get("canonical"))) for r in dec_rows]
+            grp, _members, inv_items = ops.invariant_prefix_work(dec_rows, dec_mode)
+        inv_shared = sum(dec_mode) if (dec_mode is not None and grp) else 0            # > 0: this call decodes in the shared-prefix form
+        if grp and not inv_shared and (not grouping_pays(grp, dec_rows) or (len(dec_rows) <= ops.FUSED_ATTN_MAX_M and lm.head_dim == 128)):
             grp = []      # (up to 16 rows the one-launch RoPE + KV write + attention kernel beats the three launches of the grouped
                           #  path although it reads a shared prefix once per row: tools/small_batch_attn_probe.py, +4 ... 9 %)
         # retirement / growth of the own pools needs an EOS to retire on, per-question state that lives only in the runner's row order
@@ -1377,9 +1411,10 @@ class VddLlavaEngine:
         retire = bool(self.retire and eos_token_id is not None and not output_scores and streamer is None and not (proc and proc.get("python"))
                       and not grp and max_new_tokens > self.kv_chunk and (ops.GEMM_BATCH_INVARIANT or not deterministic) and not reuse_prefill)
         own_cap = min(max_new_tokens, self.kv_chunk) if retire else max_new_tokens
+        pool_form = "shared" if inv_shared else bool(grp)         # (the key of VddLlavaEngine.kv's cache of this form)
         kv = self.kv(len(plan["prefix"]), max([s_.get("full_T", s_["T"]) for s_ in plan["prefix"]] + [0]), len(plan["suffix"]),
-                     suffix_max + own_cap, frag_only=bool(grp))
-        if hit is not None and (kv is not hit["kv"] or bool(grp) != hit["frag"]):
+                     suffix_max + own_cap, frag_only=bool(grp) and not inv_shared, with_frag=bool(inv_shared))
+        if hit is not None and (kv is not hit["kv"] or pool_form != hit["frag"]):
             raise RuntimeError("reuse_prefill: the pools of the kept prefill were replaced")       # (cannot happen: same plan, no more new tokens)
         if hit is None:
             self._forget_kept_prefill(kv)
@@ -1411,25 +1446,26 @@ class VddLlavaEngine:
                 passes.append(pd)
             if plan["prefix"] and kv.frag_only:
                 (frag_plen,) = h2d_int32(dev, [s_.get("full_T", s_["T"]) for s_ in plan["prefix"]])
+            elif plan["prefix"] and kv.with_frag:                # fragment images of the canonical slots only (length 0: nothing is built)
+                (frag_plen,) = h2d_int32(dev, [s_.get("full_T", s_["T"]) if s_.get("canonical") else 0 for s_ in plan["prefix"]])
             passes.append(self._prefill_pass(plan["suffix"], to_prefix_pool=False, last=True, packs=True, keep_q=want_maps))
             resid, delta = self.lm.prefill(passes, kv, frag_plen=frag_plen)[-1]
             logits0 = self.lm.logits(resid, delta)                                        # [nb*Q, V], rows ordered branch-major
             if rkey is not None:
-                self._reuse_store(rkey, kv, bool(grp), plan, branches, logits0, max_new_tokens)
+                self._reuse_store(rkey, kv, pool_form, plan, branches, logits0, max_new_tokens)
         self.debug_logits0 = logits0
         attn_maps = self._attention_map(plan, passes, kv) if want_maps else None
 
         # ---- step 0: sample from the prefill logits (eager; also yields the top-n for calibration) -----------
         ctr0 = self._philox_counter(seed)
         eos_t = h2d_long(dev, eos_token_id) if eos_token_id is not None else None
-        cfgkey = (Q, nb, max_new_tokens, alpha, beta, warp.t, warp.k, warp.p, use_cd, use_dd, use_dd_unk, cd_greedy,
-                  tuple(eos_token_id) if eos_token_id is not None else None, pad_token_id, output_scores, ops.GEMM_BATCH_INVARIANT, ops.W8_DECODE)
-        cpi = ops.prefix_chunks_per_item(grp, lm.n_heads)
-        n_groups, n_items = len(grp), len(ops.prefix_work_items(grp, cpi))
-        cfgkey = cfgkey + (n_groups, n_items, cpi, proc_key)
+        cfgkey = self._step_key(Q, nb, max_new_tokens, alpha, beta, warp, use_cd, use_dd, use_dd_unk, cd_greedy, eos_token_id, pad_token_id, output_scores)
+        cpi = ops.INVARIANT_PREFIX_CHUNKS if inv_shared else ops.prefix_chunks_per_item(grp, lm.n_heads)
+        n_groups, n_items = len(grp), len(inv_items) if inv_shared else len(ops.prefix_work_items(grp, cpi))
+        cfgkey = cfgkey + (n_groups, n_items, cpi, inv_shared, proc_key)
         run = self._runner(cfgkey, Q, len(keep), max_new_tokens, dict(alpha=alpha, beta=beta, warp=warp, contrast=contrast,
                            is_vcd=use_cd, both=(use_dd and use_dd_unk), greedy=cd_greedy, eos_t=eos_t, pad=pad_token_id,
-                           output_scores=output_scores, n_groups=n_groups, n_items=n_items, cpi=cpi, proc=proc), kv)
+                           output_scores=output_scores, n_groups=n_groups, n_items=n_items, cpi=cpi, proc=proc, inv_shared=inv_shared), kv)
         run.reset(ctr0)
         if proc:
             run.set_processor_inputs(**self._processor_inputs(proc, prompt_lens, ids_list, min_new_tokens, min_length))
@@ -1453,7 +1489,7 @@ class VddLlavaEngine:
                     branch_top[bname] = (rb.top_tok, rb.top_prob)
         # the VCD branch has no state of its own after step 0 (quirk #1): only the other branches keep decoding
         run.load(pos=[seg[i]["pos0"] + seg[i]["T"] for i in sel], cpos=[seg[i]["T"] for i in sel], slot=[seg[i]["slot"] for i in sel],
-                 rows=dec_rows)
+                 rows=dec_rows, row_mode=dec_mode if inv_shared else None)
         n_new = 1
         if events is not None:
             events[1].record(torch.cuda.current_stream(dev))
@@ -1530,6 +1566,7 @@ class VddLlavaEngine:
         stats["steps"] = int(gen.shape[1])
         stats["graph"] = run.graph is not None
         stats["n_groups"] = n_groups          # > 0: the decode steps ran the grouped (shared-prefix) attention
+        stats["shared_rows"] = inv_shared     # > 0: ... in the batch-invariant mode's form (ops.INVARIANT_SHARED_PREFIX), for that many decode rows
         return GenerateOutput(seqs_out, gen, scores, top_prob, top_tok, stats,
                               attentions=StepAttentions(attn_maps, lm.n_layers, int(gen.shape[1])) if attn_maps is not None else None, branch_top=branch_top)
 
@@ -1565,6 +1602,10 @@ class VddLlavaEngine:
         deterministic decode; a sampled decode draws a preempted question afresh (still reproducible for a seed: the schedule depends
         only on the polled finished flags).  in_flight is then only lowered when not even the staging pool + one question fit."""
         dev, lm = self.device, self.cfg.lm
+        if ops.invariant_shared_prefix():
+            # this call never groups: its image rows would take the per-row arithmetic and no longer equal generate()'s under the flag
+            raise ValueError("generate_list has no shared-prefix form: leave ops.INVARIANT_SHARED_PREFIX (batch_invariant(shared_prefix=True), "
+                             "--invariant-shared-prefix) off for it, or use generate()")
         if eos_token_id is None:
             raise ValueError("generate_list needs eos_token_id: without an EOS every answer has max_new_tokens tokens and generate() in batches does the same work")
         if pad_token_id is None:
@@ -2008,12 +2049,21 @@ class VddLlavaEngine:
     # its plan, pools and step-0 logits; the next reuse_prefill call with the same prompt and image tensors (the caller's promise: unchanged),
     # the same branches and no more new tokens skips the vision tower and the prefill and decodes again from that state (a decode only writes
     # own-KV positions behind the prompt).  Not with the VCD branch (fresh noise per call); such calls never retire rows.
+    @staticmethod
+    def _step_key(Q, nb, max_new_tokens, alpha, beta, warp, use_cd, use_dd, use_dd_unk, cd_greedy, eos_token_id, pad_token_id, output_scores):
+        """What a captured decode step of generate() is kept under (the call appends its grouping and processor configuration): a graph is
+        never replayed in another mode - batch-invariant or tuned, shared-prefix form or per-row, 8-bit codes or not."""
+        return (Q, nb, max_new_tokens, alpha, beta, warp.t, warp.k, warp.p, use_cd, use_dd, use_dd_unk, cd_greedy,
+                tuple(eos_token_id) if eos_token_id is not None else None, pad_token_id, output_scores, ops.GEMM_BATCH_INVARIANT, ops.W8_DECODE,
+                ops.invariant_shared_prefix())
+
     def _reuse_lookup(self, ids_list, images, embs, embeds_prefix, branch_flags, share_prefix, max_new_tokens):
         """-> (the kept state if it serves this call, else None; the key to keep this call's state under)"""
         ims = None if images is None else tuple((images[i].data_ptr(), tuple(images[i].shape)) for i in range(len(ids_list)))
         embs = None if embs is None else tuple((e.data_ptr(), tuple(e.shape)) for e in embs)
         key = (tuple(map(tuple, ids_list)), ims, embs, tuple(embeds_prefix) if embeds_prefix is not None else None, branch_flags, share_prefix,
-               self.two_level_prefix, self.share_repeated_rows, self.group_attention, ops.GEMM_BATCH_INVARIANT, str(self.dtype))
+               self.two_level_prefix, self.share_repeated_rows, self.group_attention, ops.GEMM_BATCH_INVARIANT, str(self.dtype),
+               ops.invariant_shared_prefix())
         c = self._prefill_cache
         hit = c is not None and c["key"] == key and self._kvs.get(c["frag"]) is c["kv"] and max_new_tokens <= c["max_new"]
         return (c if hit else None), key
@@ -2111,7 +2161,7 @@ class VddLlavaEngine:
         if best is None or len(best[1]) < 2 or len(best[0]) < min_tokens or len(best[0]) * (len(best[1]) - 1) < min_saved:
             return
         toks, members = list(best[0]), best[1]
-        parent = dict(slot=len(plan["prefix"]), tokens=toks, img=None, T=len(toks), pos0=0, pslot=0, plen=0)
+        parent = dict(slot=len(plan["prefix"]), tokens=toks, img=None, T=len(toks), pos0=0, pslot=0, plen=0, canonical=False)
         plan["prefix"].append(parent)
         n = len(toks)
         for s_ in members:
@@ -2131,7 +2181,11 @@ class VddLlavaEngine:
     def _plan(self, branches, n_img_tok, share_prefix, embeds_only=False, embeds_prefix=None):
         """Every (branch, question) sequence = [prefix | suffix].  Prefix = everything up to and including the
         image slot (main/cd: system prompt + 576 patch embeddings; unk: system prompt + <unk>; none: system prompt);
-        identical prefixes (same tokens, same image features) are prefilled ONCE into a prefix slot."""
+        identical prefixes (same tokens, same image features) are prefilled ONCE into a prefix slot.
+        Every prefix slot is marked `canonical` or not: True where the cut is a property of the prompt, the same in every batch - an image
+        prefix (system prompt + patches) or a caller-declared embeds_prefix; False where it follows the batch - repeated image-free rows,
+        the common leading tokens of text-only prompts, embeddings shared by the branches of one call (ops.INVARIANT_SHARED_PREFIX groups
+        decode rows by canonical slots only)."""
         prefix_slots: Dict[tuple, dict] = {}
         prefix, suffix = [], []
         n_slots, max_len, unshared = 0, 0, 0
@@ -2160,13 +2214,13 @@ class VddLlavaEngine:
                         n_pre = int(embeds_prefix[qi][1])
                         pkey = ("emb", id(feats), embeds_prefix[qi][0], n_pre)
                         if pkey not in prefix_slots:
-                            prefix_slots[pkey] = dict(slot=len(prefix), tokens=[], img=feats[qi][:n_pre], T=n_pre, pos0=0, pslot=0, plen=0)
+                            prefix_slots[pkey] = dict(slot=len(prefix), tokens=[], img=feats[qi][:n_pre], T=n_pre, pos0=0, pslot=0, plen=0, canonical=True)
                             prefix.append(prefix_slots[pkey])
                         suffix.append(dict(slot=len(suffix), tokens=None, pre=[], img=feats[qi][n_pre:], suf=[], T=T - n_pre, pos0=n_pre,
                                            pslot=prefix_slots[pkey]["slot"], plen=n_pre))
                     elif emb_uses.get(key, 0) >= 2 and T > 1:
                         if key not in prefix_slots:
-                            prefix_slots[key] = dict(slot=len(prefix), tokens=[], img=feats[qi][: T - 1], T=T - 1, pos0=0, pslot=0, plen=0)
+                            prefix_slots[key] = dict(slot=len(prefix), tokens=[], img=feats[qi][: T - 1], T=T - 1, pos0=0, pslot=0, plen=0, canonical=False)
                             prefix.append(prefix_slots[key])
                         ps = prefix_slots[key]["slot"]
                         suffix.append(dict(slot=len(suffix), tokens=None, pre=[], img=feats[qi][T - 1:], suf=[], T=1, pos0=T - 1, pslot=ps, plen=T - 1))
@@ -2211,7 +2265,7 @@ class VddLlavaEngine:
                         raise ValueError("prompt must not end with the image token")
                 if share_prefix and plen > 0:
                     if key not in prefix_slots:
-                        prefix_slots[key] = dict(slot=len(prefix), tokens=pre_tok, img=img, T=plen, pos0=0, pslot=0, plen=0)
+                        prefix_slots[key] = dict(slot=len(prefix), tokens=pre_tok, img=img, T=plen, pos0=0, pslot=0, plen=0, canonical=img is not None)
                         prefix.append(prefix_slots[key])
                     ps = prefix_slots[key]["slot"]
                     suffix.append(dict(slot=len(suffix), tokens=suf_tok, img=None, T=len(suf_tok), pos0=plen, pslot=ps, plen=plen))

@@ -24,7 +24,7 @@ import torch
 
 from . import calibrate as C
 from . import shard
-from .driver_common import (ShardedRun, add_common_args, load_kw, add_script_args, answer_text, eos_set, finish_distributed, plain_kw, read_questions, setting_kw,
+from .driver_common import (ShardedRun, add_common_args, load_kw, mode_kw, add_script_args, answer_text, eos_set, finish_distributed, plain_kw, read_questions, setting_kw,
                             sweep_result, sweep_settings, write_jsonl)
 from .engine import IMAGE_TOKEN_INDEX, VddLlavaEngine
 from .vcd_add_noise import add_diffusion_noise
@@ -105,7 +105,7 @@ def run_mme(engine: VddLlavaEngine, questions: Sequence[dict], build_inputs: Cal
             max_new_tokens: int = 20, min_new_tokens: Optional[int] = None, noise_step: Optional[int] = None,
             gt: Optional[Dict[tuple, str]] = None, results_root: Optional[str] = None, experiment: str = "exp",
             subsets: Optional[Sequence[str]] = MME_SUBSETS, chunk: Optional[tuple] = None, rank: Optional[int] = None,
-            world: Optional[int] = None, batch_invariant: Optional[bool] = None, sweep: Optional[Sequence[dict]] = None, **generate_kw) -> dict:
+            world: Optional[int] = None, batch_invariant: Optional[bool] = None, invariant_shared_prefix: bool = False, sweep: Optional[Sequence[dict]] = None, **generate_kw) -> dict:
     """questions: the llava_mme.jsonl lines (question_id 'category/image.ext', image, text, category); subsets filters them as the
     reference does; chunk=(n, k) takes the reference's k-th of n contiguous ceil-chunks (get_chunk, run_llava.py:32-40).
     generate_kw: cd_alpha, cd_beta, use_dd, use_dd_unk, temperature, top_p, top_k, seed - the reference's generate kwargs; the Qwen
@@ -124,7 +124,7 @@ def run_mme(engine: VddLlavaEngine, questions: Sequence[dict], build_inputs: Cal
     qs_all = [q for q in questions if subsets is None or q.get("category") in subsets]
     if chunk is not None:
         qs_all = [qs_all[i] for i in shard.get_chunk(len(qs_all), chunk[0], chunk[1], group=1)]
-    run = ShardedRun(qs_all, rank, world, generate_kw, batch_invariant)       # an image's two questions adjacent: shared features
+    run = ShardedRun(qs_all, rank, world, generate_kw, batch_invariant, invariant_shared_prefix)       # an image's two questions adjacent: shared features
     decode_token = lambda t: decode([t])
     settings = sweep_settings(sweep)
     if not settings:
@@ -276,7 +276,7 @@ def main(argv=None):
     # ONE pass over the question file for all settings: a batch's vision-tower pass and prefills are shared by its settings (run_mme, `sweep`)
     res = run_mme(eng, questions, build, decode, model_id=os.path.basename(a.model_path.rstrip("/")), batch_questions=a.batch, gt=gt,
                   results_root=os.path.join(os.path.dirname(os.path.abspath(sweep[0]["answers_path"])), "eval_tool_answers") if gt else None,
-                  chunk=(a.num_chunks, a.chunk_idx) if a.num_chunks > 1 else None, rank=rank, world=world, sweep=sweep, **gen_kw, **run_kw, **extra)
+                  chunk=(a.num_chunks, a.chunk_idx) if a.num_chunks > 1 else None, rank=rank, world=world, sweep=sweep, **mode_kw(a), **gen_kw, **run_kw, **extra)
     for s_ in sweep:
         r_ = res["runs"][s_["tag"]]
         out_scores[s_["tag"]] = {k: (v and {"Perception": v["Perception"]["total"], "Cognition": v["Cognition"]["total"]}) for k, v in r_["scores"].items()}

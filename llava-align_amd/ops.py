@@ -26,6 +26,7 @@ _SIGS = {
     "vdd_decode_attention": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _L, _I, _I, _F, _I, _P],
     "vdd_prefix_fragments": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vdd_decode_attention_grouped": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _L, _I, _L, _I, _I, _I, _I, _F, _I, _P],
+    "vdd_decode_attention_shared_invariant": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _L, _I, _L, _I, _I, _I, _I, _I, _F, _I, _P],
     "vdd_flash_attention": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _L, _I, _F, _I, _I, _P],
     "vdd_flash_attention_packed": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _L, _I, _F, _I, _P],
     "vdd_layernorm": [_P, _P, _P, _P, _I, _I, _F, _I, _P],
@@ -655,8 +656,10 @@ GEMM_BATCH_INVARIANT = False    # True = batch-invariant mode: a row's results n
                                 #     order whatever the macro tile; stream-K cuts K where the batch shape puts the cut, the weight-streaming kernels split
                                 #     K over waves): skinny_rows() = 0, no norm-fused layer, no split-K slabs;
                                 #   * decode attention: rope_kv_write + the per-row split-KV kernel (fixed 64-key chunks merged in key order) for every batch -
-                                #     no one-launch kernel for few rows, no grouped prefix pass (its chunking follows the batch): fused_attention_rows() = 0,
-                                #     engine: no grouping;
+                                #     no one-launch kernel for few rows, none of the TUNED grouped forms (item size, chunk rotation, own-merge threshold and the
+                                #     grouping_pays rule all follow the batch): fused_attention_rows() = 0, engine: no grouping.  With INVARIANT_SHARED_PREFIX
+                                #     (opt-in, below) rows behind an image prefix or a declared embeds_prefix take decode_attention_shared_invariant instead: the
+                                #     MFMA prefix pass with every one of those batch dependencies removed, once per image;
                                 #   * prefill: unchanged - its planning choices (prefix sharing, two-level prefixes, packs of four short suffixes) move
                                 #     WHERE a key is read from, not the order keys are summed in (64-key tiles at global key indices): measured bit-identical.
                                 # What it buys: 1-GPU and N-GPU runs of a deterministic decode (cd_greedy / top_k = 1) agree token for token,
@@ -671,16 +674,32 @@ FLASH_PACKS_IN_INVARIANT_MODE = True    # packs of four short suffixes per atten
                                         # tests/test_batch_invariant_gpu.py) - so they stay on in the mode, like two-level prefixes and prefix sharing
 
 
+INVARIANT_SHARED_PREFIX = False  # batch-invariant mode only (it means nothing outside): rows whose prefix cut is a property of the prompt - an image prefix,
+                                 # a declared embeds_prefix - attend that prefix through decode_attention_shared_invariant, once per image.  Still invariant
+                                 # (same bits alone, in any batch, on any number of ranks), but NOT the bits of the flag-off mode: the MFMA pass rounds P to
+                                 # the storage type.  Off by default; `with ops.batch_invariant(shared_prefix=True):` scopes it.
+INVARIANT_PREFIX_CHUNKS = 2      # 64-key chunks per work item of that prefix pass, for EVERY batch: the item size places the cuts of the prefix's online
+                                 # softmax, so it is part of the arithmetic - changing it changes bits.  Never tuned per call.  How the value was chosen
+                                 # (tools/invariant_prefix_probe.py, profiles/invariant_shared_prefix.jsonl): DESIGN 6c.
+
+
+def invariant_shared_prefix() -> bool:
+    """Whether decode steps take the shared-prefix form of the batch-invariant mode: the flag counts inside the mode only."""
+    return bool(GEMM_BATCH_INVARIANT and INVARIANT_SHARED_PREFIX)
+
+
 @contextlib.contextmanager
-def batch_invariant(on: bool = True):
-    """Scope of the batch-invariant mode (GEMM_BATCH_INVARIANT above).  Captured decode steps are keyed by the mode, so entering or
-    leaving it never replays a graph of the other form."""
-    global GEMM_BATCH_INVARIANT
-    old, GEMM_BATCH_INVARIANT = GEMM_BATCH_INVARIANT, bool(on)
+def batch_invariant(on: bool = True, shared_prefix: bool = False):
+    """Scope of the batch-invariant mode (GEMM_BATCH_INVARIANT above) and of its shared-prefix form (INVARIANT_SHARED_PREFIX); both are
+    restored on exit, after an exception as well.  Captured decode steps are keyed by both, so entering or leaving never replays a graph
+    of another form."""
+    global GEMM_BATCH_INVARIANT, INVARIANT_SHARED_PREFIX
+    old = (GEMM_BATCH_INVARIANT, INVARIANT_SHARED_PREFIX)
+    GEMM_BATCH_INVARIANT, INVARIANT_SHARED_PREFIX = bool(on), bool(shared_prefix)
     try:
         yield
     finally:
-        GEMM_BATCH_INVARIANT = old
+        GEMM_BATCH_INVARIANT, INVARIANT_SHARED_PREFIX = old
 
 
 def _gemm_workspace(device, M, N):
@@ -1300,6 +1319,57 @@ def decode_attention_grouped(q, k_cache, v_cache, k_prefix, v_prefix, rows, grou
                                                 out.data_ptr(), ws.data_ptr(), M, H, Hkv, D, k_cache.stride(0), k_cache.shape[2],
                                                 k_prefix.stride(0), k_prefix.shape[2], int(max_prefix_len), int(max_own_len),
                                                 int(chunks_per_item), D ** -0.5 if scale is None else scale, dt, _st(q)))
+    return out
+
+
+def invariant_prefix_work(rows, row_mode, chunks_per_item=None):
+    """Host side of decode_attention_shared_invariant: rows [[slot, len, pslot, plen], ...] and row_mode (1 = shared, 0 = per row) ->
+    (groups [[row_off, n_rows, pslot, plen]], group_rows, items [[group, first_row, item, 0]]).  Every shared row is in exactly one group
+    of the rows with its (pslot, plen) - a group of one where nobody else reads that prefix; per-row rows are in none.  Items have the
+    ONE size chunks_per_item (default INVARIANT_PREFIX_CHUNKS) whatever the batch: sum over groups of ceil(n_rows / 16) *
+    ceil(plen / (64 * chunks_per_item)) of them, longest first (order cannot matter: a partial depends on its own row alone)."""
+    cpi = INVARIANT_PREFIX_CHUNKS if chunks_per_item is None else int(chunks_per_item)
+    if cpi < 1:
+        raise ValueError("chunks_per_item must be >= 1")
+    by = {}
+    for i, ((_, _, ps, pl), m) in enumerate(zip(rows, row_mode)):
+        if m and pl > 0:
+            by.setdefault((int(ps), int(pl)), []).append(i)
+    groups, members = [], []
+    for (ps, pl), idx in by.items():
+        groups.append([len(members), len(idx), ps, pl])
+        members += idx
+    return groups, members, prefix_work_items(groups, cpi)
+
+
+def decode_attention_shared_invariant(q, k_cache, v_cache, k_prefix, v_prefix, rows, row_mode, groups, group_rows, items, n_items, H, Hkv, D,
+                                      max_prefix_len, max_own_len, max_row_len, prefix_frag, out=None, workspace=None, chunks_per_item=None,
+                                      scale=None):
+    """The decode attention of the batch-invariant mode with INVARIANT_SHARED_PREFIX (vdd_decode_attention_shared_invariant): rows with
+    row_mode 1 attend their prefix through the MFMA pass (groups / group_rows / items from invariant_prefix_work, prefix_frag from
+    prefix_fragments) and their own keys in chunks behind it; rows with row_mode 0 are bit-identical to decode_attention.
+    max_prefix_len / max_own_len bound plen / len - plen of the shared rows, max_row_len the len of the others (0: none): they size the
+    launch and the workspace and never enter a row's arithmetic; chunks_per_item (default INVARIANT_PREFIX_CHUNKS) does."""
+    dt = _dt(q, k_cache, v_cache, k_prefix, v_prefix)
+    M = q.shape[0]
+    lib = _lib_ready()
+    r64 = lambda v: (int(v) + 63) // 64 * 64
+    lib.vdd_decode_attention_workspace_bytes.restype = C.c_int64
+    need = lib.vdd_decode_attention_workspace_bytes(M, H, D, max(r64(max_prefix_len) + r64(max_own_len), r64(max_row_len)))
+    ws = workspace if workspace is not None else _attn_ws.get((q.device,))
+    if ws is None or ws.numel() * 4 < need:
+        if workspace is not None:
+            raise ValueError("attention workspace too small")
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=q.device)
+        _attn_ws[(q.device,)] = ws
+    out = torch.empty_like(q) if out is None else out
+    cpi = INVARIANT_PREFIX_CHUNKS if chunks_per_item is None else int(chunks_per_item)
+    _lib.check(lib.vdd_decode_attention_shared_invariant(
+        q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_prefix.data_ptr(), v_prefix.data_ptr(),
+        prefix_frag.data_ptr() if prefix_frag is not None else None, rows.data_ptr(), row_mode.data_ptr(), groups.data_ptr(),
+        group_rows.data_ptr(), items.data_ptr(), int(n_items), out.data_ptr(), ws.data_ptr(), M, H, Hkv, D, k_cache.stride(0),
+        k_cache.shape[2], k_prefix.stride(0), k_prefix.shape[2], int(max_prefix_len), int(max_own_len), int(max_row_len), cpi,
+        D ** -0.5 if scale is None else scale, dt, _st(q)))
     return out
 
 

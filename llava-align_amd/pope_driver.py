@@ -23,7 +23,7 @@ import torch
 
 from . import calibrate as C
 from . import shard
-from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, load_kw, answer_text, cut_at_eos, distinct, eos_set, finish_distributed,  # noqa: F401 (cut_at_eos: re-exported)
+from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, load_kw, mode_kw, answer_text, cut_at_eos, distinct, eos_set, finish_distributed,  # noqa: F401 (cut_at_eos: re-exported)
                             plain_kw, pope_scores_for, read_questions, to_all_rows, write_jsonl)
 from .engine import IMAGE_TOKEN_INDEX, VddLlavaEngine
 from .vcd_add_noise import add_diffusion_noise
@@ -41,7 +41,7 @@ def run_pope(engine: VddLlavaEngine, questions: Sequence[dict], encode: Callable
              decode: Callable[[List[int]], str], load_image: Callable[[str], torch.Tensor], answers_path: Optional[str] = None,
              model_id: str = "llava-align_amd", batch_questions: int = 384, unk_token_id: int = 0, eos_token_id=None,
              pad_token_id: Optional[int] = None, stop_str: Optional[str] = "</s>", max_new_tokens: int = 64, noise_step: Optional[int] = None,
-             rank: Optional[int] = None, world: Optional[int] = None, batch_invariant: Optional[bool] = None,
+             rank: Optional[int] = None, world: Optional[int] = None, batch_invariant: Optional[bool] = None, invariant_shared_prefix: bool = False,
              image_priors: Sequence[str] = (), reuse_unk_branch: bool = True, image_workers: int = 8, **generate_kw) -> dict:
     """questions: dicts with question_id, image, text, label (the POPE json lines).  generate_kw: cd_alpha, cd_beta, use_dd,
     use_dd_unk, temperature, top_p, top_k, seed ... exactly the reference's model.generate kwargs (llava_calibrate.py:161-177);
@@ -52,7 +52,8 @@ def run_pope(engine: VddLlavaEngine, questions: Sequence[dict], encode: Callable
     question list, decodes its contiguous chunk of whole images (shard.ShardPlan), the per-question results are gathered in ONE
     collective, and rank 0 writes the answers file; every rank returns the full result.  An explicit `seed` is offset by the rank
     (sampled runs then differ from a 1-rank run).  Deterministic decodes (cd_greedy / top_k = 1 / do_sample = False) run in
-    batch-invariant mode unless `batch_invariant=False` (shard.resolve_batch_invariant, ops.GEMM_BATCH_INVARIANT): their answers are
+    batch-invariant mode unless `batch_invariant=False` (shard.resolve_batch_invariant, ops.GEMM_BATCH_INVARIANT; invariant_shared_prefix=True: its
+    shared-prefix form, ops.INVARIANT_SHARED_PREFIX - an image prefix is read once per image again, no effect outside the mode): their answers are
     then token for token the same on 1 and on N ranks and for every batch_questions; with the tuned kernel forms (the default for
     sampled runs) a row's low-order bits depend on who shares its batch.
     image_priors: further content-free passes that keep the image prompt and swap the IMAGE - 'noise' = add_diffusion_noise(image, 999),
@@ -66,7 +67,7 @@ def run_pope(engine: VddLlavaEngine, questions: Sequence[dict], encode: Callable
     image_priors = tuple(image_priors)
     if any(n_ not in ("noise", "zeros", "ones") for n_ in image_priors):
         raise ValueError("image_priors must be among 'noise', 'zeros', 'ones'")
-    run = ShardedRun(questions, rank, world, generate_kw, batch_invariant)
+    run = ShardedRun(questions, rank, world, generate_kw, batch_invariant, invariant_shared_prefix)
     mine, generate_kw = run.mine, run.generate_kw
     decode_token = lambda t: decode([t])
     rows = run.rows(engine.device, max_new_tokens, pad_token_id, n_sets=3 + len(image_priors))
@@ -193,7 +194,7 @@ def main(argv=None):
                    unk_token_id=tok.unk_token_id if tok.unk_token_id is not None else 0, eos_token_id=tok.eos_token_id,
                    pad_token_id=tok.pad_token_id or 0, max_new_tokens=a.max_new_tokens, noise_step=a.noise_step, use_dd=a.use_dd,
                    use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, temperature=a.temperature, top_p=a.top_p, top_k=a.top_k,
-                   rank=rank, world=world, image_priors=tuple(a.image_priors), **extra)
+                   rank=rank, world=world, image_priors=tuple(a.image_priors), **mode_kw(a), **extra)
     if rank == 0:
         nan = {k: v["nan_rows"] for k, v in res["scores"].items() if isinstance(v, dict) and v.get("nan_rows")}
         print(json.dumps({"scores": res["scores"], "batch_invariant": res["batch_invariant"], "world": world,

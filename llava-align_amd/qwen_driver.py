@@ -29,7 +29,7 @@ import torch
 
 from . import calibrate as C
 from . import shard
-from .driver_common import (ShardedRun, add_common_args, load_kw, add_script_args, answer_text, chunk_of, distinct, eos_set, finish_distributed, load_distinct_images,
+from .driver_common import (ShardedRun, add_common_args, load_kw, mode_kw, add_script_args, answer_text, chunk_of, distinct, eos_set, finish_distributed, load_distinct_images,
                             plain_kw, pope_scores_for, read_questions, setting_kw, sweep_result, sweep_settings, to_all_rows, write_jsonl)
 from .engine import VddLlavaEngine
 
@@ -63,7 +63,7 @@ def run_qwen_pope(engine: VddLlavaEngine, questions: Sequence[dict], embed_promp
                   answers_path: Optional[str] = None, model_id: str = "qwen-vl", batch_questions: int = 128, eos_token_id=151643,
                   pad_token_id: Optional[int] = 151643, max_new_tokens: int = 20, min_new_tokens: Optional[int] = 1, use_cd: bool = False,
                   noise_step: int = 500, priors: Sequence[str] = PRIORS, prompt_format: str = POPE_PROMPT, rank: Optional[int] = None,
-                  world: Optional[int] = None, batch_invariant: Optional[bool] = None, sweep: Optional[Sequence[dict]] = None, paged_kv: bool = False,
+                  world: Optional[int] = None, batch_invariant: Optional[bool] = None, invariant_shared_prefix: bool = False, sweep: Optional[Sequence[dict]] = None, paged_kv: bool = False,
                   **generate_kw) -> dict:
     """questions: POPE json lines (question_id, image, text[, label]).  load_image(name) -> the [3, S, S] tensor the model's own
     `visual.image_transform` makes of the file (qwen_calibrate.py:100-101).  generate_kw: temperature, top_p, top_k, use_dd, use_dd_unk,
@@ -83,7 +83,7 @@ def run_qwen_pope(engine: VddLlavaEngine, questions: Sequence[dict], embed_promp
     priors = tuple(priors)
     if any(p_ not in PRIORS for p_ in priors):
         raise ValueError(f"priors must be among {PRIORS}")
-    run = ShardedRun(questions, rank, world, generate_kw, batch_invariant)
+    run = ShardedRun(questions, rank, world, generate_kw, batch_invariant, invariant_shared_prefix)
     mine, generate_kw = run.mine, run.generate_kw
     decode_token = lambda t: decode([t])
     prior_kw = dict(max_new_tokens=1, n_top=10, min_new_tokens=min_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id, **plain_kw(generate_kw))
@@ -225,7 +225,7 @@ def main(argv=None):
     pope = "POPE" in a.question_file
     common = dict(image_path=lambda f: os.path.join(a.image_folder, f), model_id="qwen-vl" if "Chat" not in a.model_path else "qwen-vl-chat",
                   batch_questions=a.batch, eos_token_id=tok.eod_id, pad_token_id=tok.eod_id, use_cd=a.use_cd, noise_step=a.noise_step, rank=rank, world=world,
-                  use_dd=a.use_dd, use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, seed=a.seed, paged_kv=getattr(a, "paged_kv", False))
+                  use_dd=a.use_dd, use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, seed=a.seed, paged_kv=getattr(a, "paged_kv", False), **mode_kw(a))
     if a.sampling and pope and len(runs) > 1:
         # the POPE sampling sweep (answers of <= 20 tokens): every setting from ONE pass over the question file, a batch's prefill shared by its settings
         sweep = [dict(tag=tag, temperature=temp, top_p=top_p, top_k=top_k, answers_path=os.path.expanduser(a.answers_file).replace("setting", tag))

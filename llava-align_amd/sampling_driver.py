@@ -16,7 +16,7 @@ from typing import Callable, List, Optional, Sequence
 import torch
 
 from . import shard
-from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, load_kw, add_script_args, answer_text, chunk_of, eos_set, finish_distributed, load_distinct_images, read_questions,
+from .driver_common import (QUESTION_SUFFIX, ShardedRun, add_common_args, load_kw, mode_kw, add_script_args, answer_text, chunk_of, eos_set, finish_distributed, load_distinct_images, read_questions,
                             write_jsonl)
 from .engine import VddLlavaEngine
 from .vcd_add_noise import add_diffusion_noise
@@ -33,7 +33,7 @@ def run_sampling(engine: VddLlavaEngine, questions: Sequence[dict], encode: Call
                  load_image: Callable[[str], torch.Tensor], answers_path: Optional[str] = None, model_id: str = "llava-align_amd",
                  pope_suffix: bool = False, in_flight: int = 90, max_new_tokens: int = 1024, eos_token_id=2, pad_token_id: Optional[int] = 0,
                  stop_str: Optional[str] = "</s>", noise_step: Optional[int] = None, rank: Optional[int] = None, world: Optional[int] = None,
-                 batch_invariant: Optional[bool] = None, paged_kv: bool = False, **generate_kw) -> dict:
+                 batch_invariant: Optional[bool] = None, invariant_shared_prefix: bool = False, paged_kv: bool = False, **generate_kw) -> dict:
     """questions: dicts with question_id, image, text.  generate_kw: cd_alpha, cd_beta, use_dd, use_dd_unk, temperature, top_p, top_k, seed,
     cd_greedy - the reference's generate kwargs (llava_sampling.py:96-109; temperature 0 there means greedy: pass do_sample=False).
     rank / world (default: the initialised torch.distributed group): every rank decodes its contiguous chunk of whole images
@@ -42,7 +42,7 @@ def run_sampling(engine: VddLlavaEngine, questions: Sequence[dict], encode: Call
     paged_kv: engine.generate_list(paged_kv=True) - own-KV memory follows the tokens really generated, so `in_flight` questions fit at
     max_new_tokens=1024 where full-length slots would not.
     Returns {"answers": [...], "stats": the engine's stats of this rank's chunk}."""
-    run = ShardedRun(questions, rank, world, generate_kw, batch_invariant)
+    run = ShardedRun(questions, rank, world, generate_kw, batch_invariant, invariant_shared_prefix)
     mine, generate_kw = run.mine, run.generate_kw
     imgs = load_distinct_images([questions[i]["image"] for i in mine], load_image, engine.device)       # the SAME tensor for questions about one image: shared features / prefix
     ids = [torch.tensor(encode(llava_v1_user_prompt("<image>\n" + questions[i]["text"] + (QUESTION_SUFFIX if pope_suffix else "")))) for i in mine]
@@ -125,7 +125,7 @@ def main(argv=None):
                            model_id=os.path.basename(a.model_path.rstrip("/")), pope_suffix=a.naive or "POPE" in a.question_file, in_flight=a.in_flight,
                            max_new_tokens=a.max_new_tokens, eos_token_id=tok.eos_token_id, pad_token_id=tok.pad_token_id or 0,
                            noise_step=a.noise_step if a.use_cd else None, rank=rank, world=world, paged_kv=getattr(a, "paged_kv", False), use_dd=a.use_dd,
-                           use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, temperature=temp if temp > 0 else 1.0, top_p=top_p, top_k=top_k, seed=a.seed, **greedy)
+                           use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, temperature=temp if temp > 0 else 1.0, top_p=top_p, top_k=top_k, seed=a.seed, **mode_kw(a), **greedy)
         if rank == 0:
             print(json.dumps({"run": tag or "naive", "answers_file": path, "n_answers": len(res["answers"]), "stats": {k: v for k, v in res["stats"].items() if not hasattr(v, "__len__") or isinstance(v, str)}}), flush=True)
     finish_distributed(world)
