@@ -396,6 +396,33 @@ int vdd_decode_attention_shared_invariant(const void* q, const void* k_cache, co
                                           int max_prefix_len, int max_own_len, int max_row_len, int prefix_chunks_per_item, float scale,
                                           int dtype, void* hip_stream);
 
+/* The two entries above for a work list that changes between replays of ONE captured launch (engine.generate_list(group_images=True):
+ * group membership moves with every admission, release and preemption, while a captured launch keeps its dimensions and scalars).
+ * groups / group_rows / items are device tables of fixed capacity that the host rewrites between replays; the prefix pass reads the
+ * number of items from *n_items_dev (device int32; values above items_capacity count as items_capacity, the size of `items` in
+ * records) and walks them with a stride, its grid sized from items_capacity (1 .. 65535) and never from the live count.  The
+ * arithmetic of an item, of the own passes and of the merges is the static entries': on equal tables the outputs are bit-identical
+ * to theirs.  A group with n_rows == 0 contributes nothing; a row listed in no group must carry prefix_len 0 (or row_mode 0).
+ * vdd_decode_attention_grouped_list with page_table != NULL reads the own keys through the page table (k_cache / v_cache = the page
+ * pools, slot_stride = the page stride, t_max unused; n_pages, n_slots, max_pages_per_slot as in vdd_decode_attention_paged) with
+ * the lane-to-key map and online-softmax order of the contiguous form: equal K / V give equal bits.  With page_table == NULL the
+ * three page arguments are ignored.  Refused before any launch (VDD_ERR_INVALID_ARG): what the static entries refuse, a null
+ * n_items_dev, items_capacity < 1 or > 65535, a null prefix_frag or prefix_tmax % 64 != 0 (the list may hold items at any replay),
+ * and with a page table what vdd_decode_attention_paged refuses.  Workspaces as for the static entries. */
+int vdd_decode_attention_grouped_list(const void* q, const void* k_cache, const void* v_cache, const int32_t* page_table, const void* k_prefix,
+                                      const void* v_prefix, const void* prefix_frag, const int32_t* rows, const int32_t* groups,
+                                      const int32_t* group_rows, const int32_t* items, const int32_t* n_items_dev, int items_capacity,
+                                      void* out, void* workspace, int M, int H, int Hkv, int D, int64_t slot_stride, int t_max, int n_pages,
+                                      int n_slots, int max_pages_per_slot, int64_t prefix_stride, int prefix_tmax, int max_prefix_len,
+                                      int max_own_len, int prefix_chunks_per_item, float scale, int dtype, void* hip_stream);
+int vdd_decode_attention_shared_invariant_list(const void* q, const void* k_cache, const void* v_cache, const void* k_prefix,
+                                               const void* v_prefix, const void* prefix_frag, const int32_t* rows, const int32_t* row_mode,
+                                               const int32_t* groups, const int32_t* group_rows, const int32_t* items,
+                                               const int32_t* n_items_dev, int items_capacity, void* out, void* workspace, int M, int H,
+                                               int Hkv, int D, int64_t slot_stride, int t_max, int64_t prefix_stride, int prefix_tmax,
+                                               int max_prefix_len, int max_own_len, int max_row_len, int prefix_chunks_per_item, float scale,
+                                               int dtype, void* hip_stream);
+
 /* Fragment-major copy of the prefix pool for the MFMA prefix pass: prefix_frag[slot][kv_head][chunk] = one 32-KiB block per
  * 64-key chunk (t_max % 64 == 0; twice the bytes and slot stride of k_prefix), 16 K fragments then 16 V^T fragments, each
  * the 1-KiB lane-linear image of one 16x16x32 MFMA operand; keys >= prefix_len_of_slot[slot] are zero-filled.  Built once

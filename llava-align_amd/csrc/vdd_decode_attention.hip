@@ -9,6 +9,10 @@
 //                                          the own keys: decode_attn_own_merge_kernel (<= 256 own keys) or decode_attn_kernel + combine
 //   vdd_decode_attention_shared_invariant  batch-invariant mode with shared prefixes: the MFMA prefix pass with a batch-free chunk walk, then
 //                                          decode_attn_mixed_kernel (per row: own chunks behind the prefix, or whole-context chunks) + combine
+//   vdd_decode_attention_grouped_list      the grouped form for a work list that changes under ONE captured launch: decode_attn_prefix_mfma_kernel<.., LIST>
+//                                          (item count from device memory, strided walk); own keys contiguous or through the page table
+//                                          (decode_attn_own_merge_paged_kernel / decode_attn_paged_own_kernel + combine)
+//   vdd_decode_attention_shared_invariant_list  the batch-invariant form on such a list (contiguous own pool)
 //   vdd_decode_attention_fused             few rows: RoPE + KV-cache write + whole-context attention + merge in ONE kernel
 //   vdd_decode_attention_fused_split       ... with the old keys split 2 or 4 ways across blocks (ticket merge)
 //   vdd_prefix_fragments                   fragment-major copy of a prefix's K / V for the MFMA prefix pass (once per generate)
@@ -196,6 +200,17 @@ __global__ void __launch_bounds__(256) decode_attn_paged_kernel(const uint16_t* 
     decode_attn_chunk<D>(q, OwnPaged<D>{k_pages, v_pages, pt}, kpre, vpre, rows, ws, H, Hkv, pre_stride, pre_tmax, scale, nchunk, 0, 0);
 }
 
+// The own chunks of the grouped form over the paged pool (vdd_decode_attention_grouped_list with a page table, own ranges above 256
+// keys): decode_attn_kernel's own_only walk behind the `npre` prefix records, keys through the page table.
+template <int D>
+__global__ void __launch_bounds__(256) decode_attn_paged_own_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k_pages,
+                                                                    const uint16_t* __restrict__ v_pages, PageTable pt,
+                                                                    const uint16_t* __restrict__ kpre, const uint16_t* __restrict__ vpre,
+                                                                    const AttnRow* __restrict__ rows, float* __restrict__ ws, int H, int Hkv,
+                                                                    long long pre_stride, int pre_tmax, float scale, int nchunk, int npre) {
+    decode_attn_chunk<D>(q, OwnPaged<D>{k_pages, v_pages, pt}, kpre, vpre, rows, ws, H, Hkv, pre_stride, pre_tmax, scale, nchunk, 1, npre);
+}
+
 // Grouped mode, short own ranges (a question's own prompt tokens + what it generated so far: <= 256 keys): ONE wave per
 // (row, head) walks the whole own range [plen, len), then folds in the row's prefix partials left by the MFMA prefix pass
 // and writes the normalised bf16 output - no own partials, no separate combine launch.
@@ -236,6 +251,67 @@ __global__ void __launch_bounds__(256) decode_attn_own_merge_kernel(const uint16
     }
     merge_lane_groups(m, l, acc);
     // fold in the prefix partials (every lane of a 16-lane group reads its 8 dims; group 0 stores)
+    const int used_pre = npre > 0 ? (ar.plen + pre_keys - 1) / pre_keys : 0;
+    const float* base = ws + ((size_t)row * H + head) * nchunk * ATT_PS;
+    for (int c = 0; c < used_pre; ++c) {
+        const float* pp = base + (size_t)c * ATT_PS;
+        const float mo = pp[D], lo_ = pp[D + 1];
+        const float mn = fmaxf(m, mo);
+        const float c0 = (m == -INFINITY) ? 0.f : __expf(m - mn), c1 = (mo == -INFINITY) ? 0.f : __expf(mo - mn);
+        const float4 a0 = *reinterpret_cast<const float4*>(pp + j * 8), a1 = *reinterpret_cast<const float4*>(pp + j * 8 + 4);
+        l = l * c0 + lo_ * c1;
+        acc[0] = acc[0] * c0 + a0.x * c1; acc[1] = acc[1] * c0 + a0.y * c1; acc[2] = acc[2] * c0 + a0.z * c1; acc[3] = acc[3] * c0 + a0.w * c1;
+        acc[4] = acc[4] * c0 + a1.x * c1; acc[5] = acc[5] * c0 + a1.y * c1; acc[6] = acc[6] * c0 + a1.z * c1; acc[7] = acc[7] * c0 + a1.w * c1;
+        m = mn;
+    }
+    if (g == 0) {
+        const float inv = 1.f / l;
+        uint4 o4;
+        o4.x = pack(acc[0] * inv, acc[1] * inv); o4.y = pack(acc[2] * inv, acc[3] * inv);
+        o4.z = pack(acc[4] * inv, acc[5] * inv); o4.w = pack(acc[6] * inv, acc[7] * inv);
+        *reinterpret_cast<uint4*>(out + ((size_t)row * H + head) * D + j * 8) = o4;
+    }
+}
+
+// decode_attn_own_merge_kernel with the own keys read through the page table (vdd_decode_attention_grouped_list with a page table):
+// the same lane-group-to-key map (group g takes own keys 4 i + g, 8 in flight), the same online-softmax order and the same fold of the
+// prefix partials, so equal K / V give equal bits.  A key without a page is read from page 0 and left out of the softmax.
+template <int D>
+__global__ void __launch_bounds__(256) decode_attn_own_merge_paged_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k_pages,
+                                                                          const uint16_t* __restrict__ v_pages, PageTable pt,
+                                                                          const AttnRow* __restrict__ rows, const float* __restrict__ ws,
+                                                                          uint16_t* __restrict__ out, int H, int Hkv, float scale, int nchunk,
+                                                                          int npre, int pre_keys) {
+    static_assert(D == 128, "lane map assumes 16 lanes x 8 dims");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int head = blockIdx.x * 4 + wave, row = blockIdx.y;
+    if (head >= H) return;
+    const int g = lane >> 4, j = lane & 15;
+    const AttnRow ar = rows[row];
+    const int kvh = head / (H / Hkv);
+    const uint4 qv = *reinterpret_cast<const uint4*>(q + ((size_t)row * H + head) * D + j * 8);
+    const auto own = OwnPaged<D>{k_pages, v_pages, pt}.at(ar, kvh, j, Hkv);      // k(tt) / v(tt) take the absolute key index plen + i
+    const int n_own = ar.len - ar.plen;
+    float m = -INFINITY, l = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    constexpr int U = 8;
+    for (int t0 = g; t0 < n_own; t0 += 4 * U) {
+        uint4 kv[U], vv[U];
+        bool there[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int t = t0 + 4 * u;
+            const int tt = ar.plen + (t < n_own ? t : n_own - 1);
+            kv[u] = ld_stream(own.k(tt));
+            vv[u] = ld_stream(own.v(tt));
+            there[u] = t < n_own && own.ok(tt);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float s = key_score(qv, kv[u], scale);
+            if (there[u]) ATT_ONLINE_STEP(s, vv[u], m, l, acc);
+        }
+    }
+    merge_lane_groups(m, l, acc);
     const int used_pre = npre > 0 ? (ar.plen + pre_keys - 1) / pre_keys : 0;
     const float* base = ws + ((size_t)row * H + head) * nchunk * ATT_PS;
     for (int c = 0; c < used_pre; ++c) {
@@ -544,126 +620,139 @@ __global__ void __launch_bounds__(256) prefix_fragments_kernel(const uint16_t* _
 // registers = 3 waves per SIMD; capped at 128 the pass is 10 % faster (tools/attn_probe.py: 314 -> 274 us per layer).
 // INVARIANT (vdd_decode_attention_shared_invariant): the chunk walk of an item may know the head, the item's index inside the prefix and
 // plen, never the group, the slice or the slot - a row's partial must not change with its neighbours.
-template <int D, bool INVARIANT = false>
+// LIST (vdd_decode_attention_grouped_list / _shared_invariant_list): a work list that changes between replays of ONE captured launch
+// (engine.generate_list(group_images=True): group membership moves with every admission, release and preemption).  The item count is
+// read from device memory (clamped to the capacity of `items`) and the blocks walk the list with a stride of gridDim.y, which the host
+// sizes from the list's capacity and the chip, never from the live count.  Which block serves an item is not part of its arithmetic:
+// the same chunk walk and rotation, the same partial record.
+template <int D, bool INVARIANT = false, bool LIST = false>
 __global__ void __launch_bounds__(256, 2) decode_attn_prefix_mfma_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ frag,
                                                                       const GroupDesc* __restrict__ groups,
                                                                       const int* __restrict__ group_rows, const int4* __restrict__ items,
                                                                       float* __restrict__ ws, int H, int Hkv, long long pre_stride,
-                                                                      int pre_tmax, float scale, int nchunk, int sub) {
+                                                                      int pre_tmax, float scale, int nchunk, int sub,
+                                                                      const int32_t* __restrict__ n_items_dev, int items_capacity) {
     static_assert(D == 128, "");
     constexpr int KS = D / 32, NT = D / 16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ln = lane & 15, g = lane >> 4;
     const int head = blockIdx.x * 4 + wave;               // head groups fastest: the (long-first) item list is walked in order
     if (head >= H) return;
-    const int4 item = items[blockIdx.y];
-    const GroupDesc gd = groups[item.x];
-    // an item = `sub` consecutive 64-key chunks (online softmax across them): one partial per (row, head, item)
-    const int r0 = item.y, part = item.z, kbeg = part * ATT_CH * sub;
-    if (r0 >= gd.n_rows || kbeg >= gd.plen) return;
-    const int k1 = min(gd.plen, kbeg + ATT_CH * sub);
-    const int kvh = head / (H / Hkv);
-    // B operand of S^T: this lane's query row
-    int rq = r0 + ln; if (rq >= gd.n_rows) rq = gd.n_rows - 1;
-    const int qrow = group_rows[gd.row_off + rq];
-    frag8_t qf[KS];
-    {
-        const uint16_t* qp = q + ((size_t)qrow * H + head) * D + g * 8;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const frag8_t*>(qp + ks * 32);
+    unsigned it = blockIdx.y, n_list = 0;
+    if constexpr (LIST) {
+        n_list = (unsigned)max(0, min(*n_items_dev, items_capacity));
+        if (it >= n_list) return;
     }
-    const uint16_t* fb = frag + 2 * ((size_t)gd.pslot * pre_stride + (size_t)kvh * pre_tmax * D) + (size_t)lane * 8;
-    f32x4_t o[NT];
+    do {            // !LIST: one pass (`continue` leaves it)
+        const int4 item = items[LIST ? it : blockIdx.y];
+        const GroupDesc gd = groups[item.x];
+        // an item = `sub` consecutive 64-key chunks (online softmax across them): one partial per (row, head, item)
+        const int r0 = item.y, part = item.z, kbeg = part * ATT_CH * sub;
+        if (r0 >= gd.n_rows || kbeg >= gd.plen) continue;
+        const int k1 = min(gd.plen, kbeg + ATT_CH * sub);
+        const int kvh = head / (H / Hkv);
+        // B operand of S^T: this lane's query row
+        int rq = r0 + ln; if (rq >= gd.n_rows) rq = gd.n_rows - 1;
+        const int qrow = group_rows[gd.row_off + rq];
+        frag8_t qf[KS];
+        {
+            const uint16_t* qp = q + ((size_t)qrow * H + head) * D + g * 8;
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) o[nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    float mrun = -INFINITY, lrun = 0.f;          // of query ln (replicated over g)
-    // Chunks in a ROTATED order (the online softmax does not care): every (group, head) stream starts at t = 0 of a region that
-    // is a multiple of 32 KiB away from the others', so waves walking in step would all sit on the same HBM channels
-    const int nch_i = (k1 - kbeg + ATT_CH - 1) / ATT_CH;
-    const int rot = (int)((unsigned)(INVARIANT ? head * 5 + part * 3 : head * 5 + item.x * 3 + r0) % (unsigned)nch_i);
-    for (int ci = 0; ci < nch_i; ++ci) {
-        const int cc = ci + rot < nch_i ? ci + rot : ci + rot - nch_i;
-        const int k0 = kbeg + cc * ATT_CH;
-        // The pass is a pure stream (one wave reads the chunk's 32-KiB block and nobody else does), so what matters is bytes in
-        // flight: ALL 32 fragment loads of the chunk are issued before the first MFMA.  Issued a few at a time behind their
-        // consumers (as the compiler schedules them under a 128-VGPR cap) the pass ran at 4.2 TB/s with 1-2 loads in flight
-        // per wave in its P V half.
-        frag8_t kf[4][KS], vf[2][NT];
-        const uint16_t* cb = fb + (size_t)(k0 / ATT_CH) * FRAG_CHUNK_ELEMS;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) kf[t][ks] = __builtin_nontemporal_load(reinterpret_cast<const frag8_t*>(cb + (t * KS + ks) * 512));
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) vf[kk][nt] = __builtin_nontemporal_load(reinterpret_cast<const frag8_t*>(cb + ATT_CH * D + (kk * NT + nt) * 512));
-        __builtin_amdgcn_sched_barrier(0);
-        // S^T: 4 tiles (a0, b0 | a1, b1); MFMA row i = ln of the A operand
-        f32x4_t s[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            s[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) s[t] = mfma16(kf[t][ks], qf[ks], s[t]);
+            for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const frag8_t*>(qp + ks * 32);
         }
-        // column = query ln; this lane's rows 4 g + r are keys k0 + 32 (t>>1) + 8 g + 4 (t&1) + r
-        float mx = -INFINITY;
+        const uint16_t* fb = frag + 2 * ((size_t)gd.pslot * pre_stride + (size_t)kvh * pre_tmax * D) + (size_t)lane * 8;
+        f32x4_t o[NT];
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
+        for (int nt = 0; nt < NT; ++nt) o[nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        float mrun = -INFINITY, lrun = 0.f;          // of query ln (replicated over g)
+        // Chunks in a ROTATED order (the online softmax does not care): every (group, head) stream starts at t = 0 of a region that
+        // is a multiple of 32 KiB away from the others', so waves walking in step would all sit on the same HBM channels
+        const int nch_i = (k1 - kbeg + ATT_CH - 1) / ATT_CH;
+        const int rot = (int)((unsigned)(INVARIANT ? head * 5 + part * 3 : head * 5 + item.x * 3 + r0) % (unsigned)nch_i);
+        for (int ci = 0; ci < nch_i; ++ci) {
+            const int cc = ci + rot < nch_i ? ci + rot : ci + rot - nch_i;
+            const int k0 = kbeg + cc * ATT_CH;
+            // The pass is a pure stream (one wave reads the chunk's 32-KiB block and nobody else does), so what matters is bytes in
+            // flight: ALL 32 fragment loads of the chunk are issued before the first MFMA.  Issued a few at a time behind their
+            // consumers (as the compiler schedules them under a 128-VGPR cap) the pass ran at 4.2 TB/s with 1-2 loads in flight
+            // per wave in its P V half.
+            frag8_t kf[4][KS], vf[2][NT];
+            const uint16_t* cb = fb + (size_t)(k0 / ATT_CH) * FRAG_CHUNK_ELEMS;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int key = k0 + (t >> 1) * 32 + g * 8 + (t & 1) * 4 + r;
-                const float v = key < k1 ? s[t][r] * scale : -INFINITY;
-                s[t][r] = v; mx = fmaxf(mx, v);
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) kf[t][ks] = __builtin_nontemporal_load(reinterpret_cast<const frag8_t*>(cb + (t * KS + ks) * 512));
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) vf[kk][nt] = __builtin_nontemporal_load(reinterpret_cast<const frag8_t*>(cb + ATT_CH * D + (kk * NT + nt) * 512));
+            __builtin_amdgcn_sched_barrier(0);
+            // S^T: 4 tiles (a0, b0 | a1, b1); MFMA row i = ln of the A operand
+            f32x4_t s[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                s[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) s[t] = mfma16(kf[t][ks], qf[ks], s[t]);
             }
-        mx = fmaxf(mx, __shfl_xor(mx, 16)); mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mnew = fmaxf(mrun, mx);                      // finite: every chunk holds >= 1 valid key
-        const float corr = __expf(mrun - mnew);                  // exp(-inf) = 0 on the first chunk
-        float lsum = 0.f;
-        frag8_t pf[2];
+            // column = query ln; this lane's rows 4 g + r are keys k0 + 32 (t>>1) + 8 g + 4 (t&1) + r
+            float mx = -INFINITY;
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
+            for (int t = 0; t < 4; ++t)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float pv = __expf(s[kk * 2 + (e >> 2)][e & 3] - mnew);      // exp(-inf) = 0 for masked keys
-                lsum += pv;
-                pf[kk][e] = (short)f2e(pv);
+                for (int r = 0; r < 4; ++r) {
+                    const int key = k0 + (t >> 1) * 32 + g * 8 + (t & 1) * 4 + r;
+                    const float v = key < k1 ? s[t][r] * scale : -INFINITY;
+                    s[t][r] = v; mx = fmaxf(mx, v);
+                }
+            mx = fmaxf(mx, __shfl_xor(mx, 16)); mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float mnew = fmaxf(mrun, mx);                      // finite: every chunk holds >= 1 valid key
+            const float corr = __expf(mrun - mnew);                  // exp(-inf) = 0 on the first chunk
+            float lsum = 0.f;
+            frag8_t pf[2];
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float pv = __expf(s[kk * 2 + (e >> 2)][e & 3] - mnew);      // exp(-inf) = 0 for masked keys
+                    lsum += pv;
+                    pf[kk][e] = (short)f2e(pv);
+                }
+            lsum += __shfl_xor(lsum, 16); lsum += __shfl_xor(lsum, 32);
+            lrun = lrun * corr + lsum;
+            mrun = mnew;
+            if (ci > 0) {           // O rows are queries 4 g + r: their rescale factor lives in the lanes of column 4 g + r
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float cr = __shfl(corr, 4 * g + r);
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) o[nt][r] *= cr;
+                }
             }
-        lsum += __shfl_xor(lsum, 16); lsum += __shfl_xor(lsum, 32);
-        lrun = lrun * corr + lsum;
-        mrun = mnew;
-        if (ci > 0) {           // O rows are queries 4 g + r: their rescale factor lives in the lanes of column 4 g + r
+            // O += P V
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float cr = __shfl(corr, 4 * g + r);
+            for (int kk = 0; kk < 2; ++kk) {
+                if (k0 + kk * 32 < k1) {
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) o[nt][r] *= cr;
+                    for (int nt = 0; nt < NT; ++nt) o[nt] = mfma16(pf[kk], vf[kk][nt], o[nt]);
+                }
             }
         }
-        // O += P V
+        // O's C layout: column ln of tile nt = dim 8 ln + nt, row = query 4 g + r
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            if (k0 + kk * 32 < k1) {
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) o[nt] = mfma16(pf[kk], vf[kk][nt], o[nt]);
+        for (int r = 0; r < 4; ++r) {
+            const int rr = r0 + g * 4 + r;
+            if (rr < gd.n_rows) {
+                const int orow = group_rows[gd.row_off + rr];
+                float* wsp = ws + (((size_t)orow * H + head) * nchunk + part) * ATT_PS + ln * 8;
+                *reinterpret_cast<float4*>(wsp) = make_float4(o[0][r], o[1][r], o[2][r], o[3][r]);
+                *reinterpret_cast<float4*>(wsp + 4) = make_float4(o[4][r], o[5][r], o[6][r], o[7][r]);
             }
         }
-    }
-    // O's C layout: column ln of tile nt = dim 8 ln + nt, row = query 4 g + r
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int rr = r0 + g * 4 + r;
-        if (rr < gd.n_rows) {
-            const int orow = group_rows[gd.row_off + rr];
-            float* wsp = ws + (((size_t)orow * H + head) * nchunk + part) * ATT_PS + ln * 8;
-            *reinterpret_cast<float4*>(wsp) = make_float4(o[0][r], o[1][r], o[2][r], o[3][r]);
-            *reinterpret_cast<float4*>(wsp + 4) = make_float4(o[4][r], o[5][r], o[6][r], o[7][r]);
+        if (g == 0 && r0 + ln < gd.n_rows) {          // (m, l) of query ln live in the lanes of column ln
+            float* wsp = ws + (((size_t)qrow * H + head) * nchunk + part) * ATT_PS;
+            *reinterpret_cast<float2*>(wsp + D) = make_float2(mrun, lrun);
         }
-    }
-    if (g == 0 && r0 + ln < gd.n_rows) {          // (m, l) of query ln live in the lanes of column ln
-        float* wsp = ws + (((size_t)qrow * H + head) * nchunk + part) * ATT_PS;
-        *reinterpret_cast<float2*>(wsp + D) = make_float2(mrun, lrun);
-    }
+    } while (LIST && (it += gridDim.y) < n_list);
 }
 
 // the combine pass over a workspace of `nchunk` partials per (row, head), the first `npre` of them prefix items of `pre_keys` keys
@@ -766,7 +855,8 @@ VDD_HIDDEN int VDD_IMPL(vdd_decode_attention_grouped)(const void* q, const void*
     if (n_items > 0 && npre > 0) {
         hipLaunchKernelGGL(decode_attn_prefix_mfma_kernel<128>, dim3((H + 3) / 4, n_items), dim3(256), 0, st,
                            (const uint16_t*)q, (const uint16_t*)prefix_frag, (const GroupDesc*)groups, group_rows,
-                           (const int4*)items, (float*)workspace, H, Hkv, (long long)prefix_stride, prefix_tmax, scale, nchunk, sub);
+                           (const int4*)items, (float*)workspace, H, Hkv, (long long)prefix_stride, prefix_tmax, scale, nchunk, sub,
+                           (const int32_t*)nullptr, 0);
     }
     if (max_own_len <= 256) {        // short own ranges: one wave per (row, head) finishes the row (own keys + prefix partials)
         hipLaunchKernelGGL(decode_attn_own_merge_kernel<128>, dim3((H + 3) / 4, M), dim3(256), 0, st, (const uint16_t*)q,
@@ -800,7 +890,93 @@ VDD_HIDDEN int VDD_IMPL(vdd_decode_attention_shared_invariant)(const void* q, co
     if (n_items > 0 && npre > 0) {
         hipLaunchKernelGGL((decode_attn_prefix_mfma_kernel<128, true>), dim3((H + 3) / 4, n_items), dim3(256), 0, st,
                            (const uint16_t*)q, (const uint16_t*)prefix_frag, (const GroupDesc*)groups, group_rows,
-                           (const int4*)items, (float*)workspace, H, Hkv, (long long)prefix_stride, prefix_tmax, scale, nchunk, sub);
+                           (const int4*)items, (float*)workspace, H, Hkv, (long long)prefix_stride, prefix_tmax, scale, nchunk, sub,
+                           (const int32_t*)nullptr, 0);
+    }
+    hipLaunchKernelGGL(decode_attn_mixed_kernel<128>, dim3((H + 3) / 4, M, nown > nrow ? nown : nrow), dim3(256), 0, st, (const uint16_t*)q,
+                       (const uint16_t*)k_cache, (const uint16_t*)v_cache, (const uint16_t*)k_prefix, (const uint16_t*)v_prefix,
+                       (const AttnRow*)rows, row_mode, (float*)workspace, H, Hkv, (long long)slot_stride, t_max, (long long)prefix_stride,
+                       prefix_tmax, scale, nchunk, npre, nown, nrow);
+    hipLaunchKernelGGL(decode_attn_combine_mixed_kernel<128>, dim3((H + 3) / 4, M), dim3(256), 0, st, (const float*)workspace,
+                       (const AttnRow*)rows, row_mode, (uint16_t*)out, H, nchunk, npre, pre_keys);
+    return ok(hipSuccess);
+}
+
+// blocks of the list form's prefix pass: enough to keep every CU of the chip busy several times over (the items are walked with a stride),
+// never more than the list can hold
+constexpr int PREFIX_LIST_BLOCKS = 2048;
+static int prefix_list_grid_y(int items_capacity, int H) {
+    const int by_chip = (PREFIX_LIST_BLOCKS + (H + 3) / 4 - 1) / ((H + 3) / 4);
+    return items_capacity < by_chip ? items_capacity : by_chip;
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_decode_attention_grouped_list)(const void* q, const void* k_cache, const void* v_cache, const int32_t* page_table,
+                                      const void* k_prefix, const void* v_prefix, const void* prefix_frag, const int32_t* rows,
+                                      const int32_t* groups, const int32_t* group_rows, const int32_t* items, const int32_t* n_items_dev,
+                                      int items_capacity, void* out, void* workspace, int M, int H, int Hkv, int D, int64_t slot_stride,
+                                      int t_max, int n_pages, int n_slots, int max_pages_per_slot, int64_t prefix_stride, int prefix_tmax,
+                                      int max_prefix_len, int max_own_len, int prefix_chunks_per_item, float scale, void* stream) {
+    if (M <= 0) return VDD_OK;
+    if (!q || !k_cache || !v_cache || !k_prefix || !v_prefix || !rows || !groups || !group_rows || !items || !out || !workspace || D != 128 ||
+        Hkv <= 0 || H % Hkv != 0 || max_own_len <= 0 || max_prefix_len < 0 || prefix_chunks_per_item < 1) return VDD_ERR_INVALID_ARG;
+    if (!n_items_dev || items_capacity < 1 || items_capacity > 65535) return VDD_ERR_INVALID_ARG;
+    if (prefix_frag == nullptr || prefix_tmax % ATT_CH != 0) return VDD_ERR_INVALID_ARG;      // the list may hold items at any replay
+    if (page_table && !paged_args_ok(k_cache, v_cache, page_table, Hkv, D, slot_stride, n_pages, n_slots, max_pages_per_slot)) return VDD_ERR_INVALID_ARG;
+    const int sub = prefix_chunks_per_item, pre_keys = ATT_CH * sub;
+    const int npre = (max_prefix_len + pre_keys - 1) / pre_keys, nown = (max_own_len + ATT_CH - 1) / ATT_CH;
+    const int nchunk = npre + nown;
+    hipStream_t st = (hipStream_t)stream;
+    const PageTable pt{page_table, n_slots, max_pages_per_slot, n_pages};
+    if (npre > 0) {
+        hipLaunchKernelGGL((decode_attn_prefix_mfma_kernel<128, false, true>), dim3((H + 3) / 4, prefix_list_grid_y(items_capacity, H)), dim3(256), 0, st,
+                           (const uint16_t*)q, (const uint16_t*)prefix_frag, (const GroupDesc*)groups, group_rows, (const int4*)items,
+                           (float*)workspace, H, Hkv, (long long)prefix_stride, prefix_tmax, scale, nchunk, sub, n_items_dev, items_capacity);
+    }
+    if (max_own_len <= 256) {
+        if (page_table)
+            hipLaunchKernelGGL(decode_attn_own_merge_paged_kernel<128>, dim3((H + 3) / 4, M), dim3(256), 0, st, (const uint16_t*)q,
+                               (const uint16_t*)k_cache, (const uint16_t*)v_cache, pt, (const AttnRow*)rows, (const float*)workspace,
+                               (uint16_t*)out, H, Hkv, scale, nchunk, npre, pre_keys);
+        else
+            hipLaunchKernelGGL(decode_attn_own_merge_kernel<128>, dim3((H + 3) / 4, M), dim3(256), 0, st, (const uint16_t*)q,
+                               (const uint16_t*)k_cache, (const uint16_t*)v_cache, (const AttnRow*)rows, (const float*)workspace,
+                               (uint16_t*)out, H, Hkv, (long long)slot_stride, t_max, scale, nchunk, npre, pre_keys);
+        return ok(hipSuccess);
+    }
+    if (page_table)
+        hipLaunchKernelGGL(decode_attn_paged_own_kernel<128>, dim3((H + 3) / 4, M, nown), dim3(256), 0, st, (const uint16_t*)q,
+                           (const uint16_t*)k_cache, (const uint16_t*)v_cache, pt, (const uint16_t*)k_prefix, (const uint16_t*)v_prefix,
+                           (const AttnRow*)rows, (float*)workspace, H, Hkv, (long long)prefix_stride, prefix_tmax, scale, nchunk, npre);
+    else
+        hipLaunchKernelGGL(decode_attn_kernel<128>, dim3((H + 3) / 4, M, nown), dim3(256), 0, st, (const uint16_t*)q,
+                           (const uint16_t*)k_cache, (const uint16_t*)v_cache, (const uint16_t*)k_prefix, (const uint16_t*)v_prefix,
+                           (const AttnRow*)rows, (float*)workspace, H, Hkv, (long long)slot_stride, t_max, (long long)prefix_stride,
+                           prefix_tmax, scale, nchunk, 1, npre);
+    launch_combine(workspace, rows, out, M, H, nchunk, npre, pre_keys, st);
+    return ok(hipSuccess);
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_decode_attention_shared_invariant_list)(const void* q, const void* k_cache, const void* v_cache, const void* k_prefix,
+                                               const void* v_prefix, const void* prefix_frag, const int32_t* rows, const int32_t* row_mode,
+                                               const int32_t* groups, const int32_t* group_rows, const int32_t* items,
+                                               const int32_t* n_items_dev, int items_capacity, void* out, void* workspace, int M, int H,
+                                               int Hkv, int D, int64_t slot_stride, int t_max, int64_t prefix_stride, int prefix_tmax,
+                                               int max_prefix_len, int max_own_len, int max_row_len, int prefix_chunks_per_item, float scale,
+                                               void* stream) {
+    if (M <= 0) return VDD_OK;
+    if (!q || !k_cache || !v_cache || !k_prefix || !v_prefix || !rows || !row_mode || !groups || !group_rows || !items || !out || !workspace ||
+        D != 128 || Hkv <= 0 || H % Hkv != 0 || max_prefix_len < 0 || max_own_len < 0 || max_row_len < 0 || max_own_len + max_row_len <= 0 ||
+        prefix_chunks_per_item < 1) return VDD_ERR_INVALID_ARG;
+    if (!n_items_dev || items_capacity < 1 || items_capacity > 65535) return VDD_ERR_INVALID_ARG;
+    if (prefix_frag == nullptr || prefix_tmax % ATT_CH != 0) return VDD_ERR_INVALID_ARG;
+    const int sub = prefix_chunks_per_item, pre_keys = ATT_CH * sub;
+    const int npre = (max_prefix_len + pre_keys - 1) / pre_keys, nown = (max_own_len + ATT_CH - 1) / ATT_CH, nrow = (max_row_len + ATT_CH - 1) / ATT_CH;
+    const int nchunk = npre + nown > nrow ? npre + nown : nrow;
+    hipStream_t st = (hipStream_t)stream;
+    if (npre > 0) {
+        hipLaunchKernelGGL((decode_attn_prefix_mfma_kernel<128, true, true>), dim3((H + 3) / 4, prefix_list_grid_y(items_capacity, H)), dim3(256), 0, st,
+                           (const uint16_t*)q, (const uint16_t*)prefix_frag, (const GroupDesc*)groups, group_rows, (const int4*)items,
+                           (float*)workspace, H, Hkv, (long long)prefix_stride, prefix_tmax, scale, nchunk, sub, n_items_dev, items_capacity);
     }
     hipLaunchKernelGGL(decode_attn_mixed_kernel<128>, dim3((H + 3) / 4, M, nown > nrow ? nown : nrow), dim3(256), 0, st, (const uint16_t*)q,
                        (const uint16_t*)k_cache, (const uint16_t*)v_cache, (const uint16_t*)k_prefix, (const uint16_t*)v_prefix,

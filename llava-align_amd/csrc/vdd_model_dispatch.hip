@@ -118,6 +118,24 @@ VDD_MODEL_FN(vdd_decode_attention_shared_invariant,
                    int max_prefix_len, int max_own_len, int max_row_len, int prefix_chunks_per_item, float scale),
              VDD_P(q, k_cache, v_cache, k_prefix, v_prefix, prefix_frag, rows, row_mode, groups, group_rows, items, n_items, out, workspace, M, H, Hkv,
                    D, slot_stride, t_max, prefix_stride, prefix_tmax, max_prefix_len, max_own_len, max_row_len, prefix_chunks_per_item, scale))
+VDD_MODEL_FN(vdd_decode_attention_grouped_list,
+             VDD_P(const void* q, const void* k_cache, const void* v_cache, const int32_t* page_table, const void* k_prefix, const void* v_prefix,
+                   const void* prefix_frag, const int32_t* rows, const int32_t* groups, const int32_t* group_rows, const int32_t* items,
+                   const int32_t* n_items_dev, int items_capacity, void* out, void* workspace, int M, int H, int Hkv, int D, int64_t slot_stride,
+                   int t_max, int n_pages, int n_slots, int max_pages_per_slot, int64_t prefix_stride, int prefix_tmax, int max_prefix_len,
+                   int max_own_len, int prefix_chunks_per_item, float scale),
+             VDD_P(q, k_cache, v_cache, page_table, k_prefix, v_prefix, prefix_frag, rows, groups, group_rows, items, n_items_dev, items_capacity, out,
+                   workspace, M, H, Hkv, D, slot_stride, t_max, n_pages, n_slots, max_pages_per_slot, prefix_stride, prefix_tmax, max_prefix_len,
+                   max_own_len, prefix_chunks_per_item, scale))
+VDD_MODEL_FN(vdd_decode_attention_shared_invariant_list,
+             VDD_P(const void* q, const void* k_cache, const void* v_cache, const void* k_prefix, const void* v_prefix, const void* prefix_frag,
+                   const int32_t* rows, const int32_t* row_mode, const int32_t* groups, const int32_t* group_rows, const int32_t* items,
+                   const int32_t* n_items_dev, int items_capacity, void* out, void* workspace, int M, int H, int Hkv, int D, int64_t slot_stride,
+                   int t_max, int64_t prefix_stride, int prefix_tmax, int max_prefix_len, int max_own_len, int max_row_len,
+                   int prefix_chunks_per_item, float scale),
+             VDD_P(q, k_cache, v_cache, k_prefix, v_prefix, prefix_frag, rows, row_mode, groups, group_rows, items, n_items_dev, items_capacity, out,
+                   workspace, M, H, Hkv, D, slot_stride, t_max, prefix_stride, prefix_tmax, max_prefix_len, max_own_len, max_row_len,
+                   prefix_chunks_per_item, scale))
 VDD_MODEL_FN(vdd_prefix_fragments,
              VDD_P(const void* k_prefix, const void* v_prefix, void* prefix_frag, const int32_t* prefix_len_of_slot, int n_slots, int Hkv, int t_max, int D),
              VDD_P(k_prefix, v_prefix, prefix_frag, prefix_len_of_slot, n_slots, Hkv, t_max, D))

@@ -385,7 +385,8 @@ class KVCache:
     `pre` + `frag` (with_frag=True: the shared-prefix form of the batch-invariant mode, ops.INVARIANT_SHARED_PREFIX) the per-layer row-major
             pools AND a per-layer fragment image beside them: rows behind a canonical prefix (image / declared embeds_prefix) attend the
             image, every other row its row-major prefix - one prefix pool more than `pre` alone.
-    Paged form (n_pages > 0, generate_list(paged_kv=True); row-major prefixes): the decode steps keep their own tokens in page pools
+    Paged form (n_pages > 0, generate_list(paged_kv=True); row-major prefixes, with with_frag=True also their fragment images:
+    generate_list(group_images=True, paged_kv=True)): the decode steps keep their own tokens in page pools
     `pk` / `pv` [n_pages, n_kv_heads, PAGE, head_dim] behind `page_table` (int32 [n_own, max_pages], indexed by own-slot id, static:
     the captured steps read it, the host rewrites it between replays); `own` shrinks to a staging area of t_own = the longest
     suffix, which the admission prefill writes and vdd_kv_pages_scatter empties into the pages."""
@@ -640,9 +641,9 @@ class LanguageModel:
         resid = ops.embed(tokens, t["embed"])
         M = tokens.shape[0]
         if kv.n_pages:                     # paged own KV: every row count takes rope_kv_write_paged + decode_attention_paged
-            if grouping is not None:
-                raise ValueError("decode_step: the grouped attention has no paged form")
-            return self._decode_layers(resid, pos, cpos, slot, attn_rows, kv, None, workspace)
+            if grouping is not None and (grouping.get("n_items_dev") is None or grouping.get("row_mode") is not None):
+                raise ValueError("decode_step: only the list form of the tuned grouped attention has a paged form")
+            return self._decode_layers(resid, pos, cpos, slot, attn_rows, kv, grouping, workspace)
         if self.fuse_norms and grouping is None and M <= ops.FUSED_ATTN_MAX_M and D == 128 and c.ffn % 128 == 0 and c.n_layers > 0:
             # few rows: the norm-fused five-launch layer or the seven-launch layer, whichever makes THIS step faster - measured once per
             # (rows, width, dtype) on the real step (both forms write the same K / V and leave the runner's state alone), then persisted
@@ -670,7 +671,29 @@ class LanguageModel:
             else:
                 a = ops.rmsnorm(resid, t[p + "ln1"], c.eps, delta=delta, resid_out=resid)
             qkv = ops.linear(a, t[p + "wqkv"], bias=t[p + "bqkv_lm"] if c.qkv_bias else None, w8=w8(p + "wqkv"))
-            if kv.n_pages:
+            if grouping is not None and grouping.get("n_items_dev") is not None:
+                # generate_list(group_images=True): group tables of fixed capacity that the host rewrites between replays, the item
+                # count in device memory; own keys from the contiguous slots or through the page table
+                g_ = grouping
+                if kv.n_pages:
+                    q = ops.rope_kv_write_paged(qkv, pos, slot, self.cs, kv.pk[i], kv.pv[i], kv.page_table, H, Hkv, D, cpos=cpos)
+                    att = ops.decode_attention_grouped_list(q, kv.pk[i], kv.pv[i], kv.kp[i], kv.vp[i], attn_rows, g_["groups"], g_["group_rows"],
+                                                            g_["items"], g_["n_items_dev"], g_["items_capacity"], H, Hkv, D, kv.t_pre, kv.own_span,
+                                                            kv.pfrag[i], workspace=g_["workspace"], chunks_per_item=g_["cpi"],
+                                                            page_table=kv.page_table)
+                else:
+                    q = ops.rope_kv_write(qkv, pos, slot, self.cs, kv.ko[i], kv.vo[i], H, Hkv, D, cpos=cpos)
+                    if g_.get("row_mode") is not None:
+                        att = ops.decode_attention_shared_invariant_list(q, kv.ko[i], kv.vo[i], kv.kp[i], kv.vp[i], attn_rows, g_["row_mode"],
+                                                                         g_["groups"], g_["group_rows"], g_["items"], g_["n_items_dev"],
+                                                                         g_["items_capacity"], H, Hkv, D, kv.t_pre, kv.t_own, g_["max_row_len"],
+                                                                         kv.pfrag[i], workspace=g_["workspace"], chunks_per_item=g_["cpi"])
+                    else:
+                        att = ops.decode_attention_grouped_list(q, kv.ko[i], kv.vo[i], kv.kp[i], kv.vp[i], attn_rows, g_["groups"],
+                                                                g_["group_rows"], g_["items"], g_["n_items_dev"], g_["items_capacity"], H, Hkv,
+                                                                D, kv.t_pre, kv.t_own, kv.pfrag[i], workspace=g_["workspace"],
+                                                                chunks_per_item=g_["cpi"])
+            elif kv.n_pages:
                 q = ops.rope_kv_write_paged(qkv, pos, slot, self.cs, kv.pk[i], kv.pv[i], kv.page_table, H, Hkv, D, cpos=cpos)
                 att = ops.decode_attention_paged(q, kv.pk[i], kv.pv[i], kv.page_table, attn_rows, H, Hkv, D, kv.kp[i], kv.vp[i],
                                                  kv.t_pre + kv.own_span, workspace)
@@ -841,6 +864,14 @@ class _DecodeRunner:
                 # the shared-prefix form of the batch-invariant mode: the row kinds (1 = behind a canonical prefix, in a group; 0 = per row)
                 # beside the group tables; a per-row row may be as long as the pools allow
                 self.grouping.update(row_mode=torch.zeros(R, **i32), max_row_len=kv.t_pre + kv.t_own if tail["inv_shared"] < R else 0)
+        if tail.get("list_groups"):
+            # generate_list(group_images=True): membership changes at every admission, release, preemption and tail shrink, a captured
+            # launch cannot - tables of fixed capacity (a group per row at the most) + the item count in device memory (load_groups)
+            lg = tail["list_groups"]
+            self.grouping = dict(groups=torch.zeros(R, 4, **i32), group_rows=torch.zeros(R, **i32), items=torch.zeros(lg["items_capacity"], 4, **i32),
+                                 n_items_dev=torch.zeros(1, **i32), items_capacity=lg["items_capacity"], cpi=lg["cpi"], workspace=self.workspace)
+            if lg["invariant"]:
+                self.grouping.update(row_mode=torch.zeros(R, **i32), max_row_len=kv.t_pre + kv.t_own)
 
     def set_processor_inputs(self, eos_min=None, prompt_tail=None, prompt_ids=None):
         """Per-call data of the processor stage into the runner's static buffers (a captured step points at them)."""
@@ -914,6 +945,21 @@ class _DecodeRunner:
         self.gen[:, 0] = self.tok
         self.step_idx.fill_(1)
         self.ctr += 1
+
+    def load_groups(self, rows, live, row_mode=None):
+        """generate_list(group_images=True): the group tables of the rows as the host knows them (rows [[slot, len, pslot, plen]] in row
+        order, live flags, row kinds of the invariant form) into the static tables the captured step reads - small copies on the stream,
+        like the page table.  Returns (groups with a live row, rows in groups)."""
+        g = self.grouping
+        groups, members, items, n = ops.list_prefix_work(rows, live, row_mode, g["cpi"], g["items_capacity"])
+        dev = self.pos.device
+        if n:
+            g_, m_, i_ = h2d_int32(dev, groups, members, items)
+            g["groups"][: len(groups)].copy_(g_); g["group_rows"][: len(members)].copy_(m_); g["items"][:n].copy_(i_)
+        g["n_items_dev"].fill_(n)
+        if row_mode is not None:
+            g["row_mode"].copy_(h2d_int32(dev, row_mode)[0])
+        return len(groups), len(members)
 
     def _take(self, old: "_DecodeRunner", q_idx: torch.Tensor) -> torch.Tensor:
         """All state but `slot` / `gen` of `old`'s questions q_idx (int64 device tensor, ascending) and their rows (branch-major in both
@@ -1125,14 +1171,15 @@ class VddLlavaEngine:
 
     # -- plumbing ---------------------------------------------------------------------------
     def kv(self, n_pre, t_pre, n_own, t_own, frag_only=False, n_pages=0, max_pages=0, with_frag=False):
-        """The KV pools for a call, one cache per pool form (KVCache.frag_only, "paged" for the paged own-KV form of generate_list, or "shared" for
-        the row-major + fragment form of the batch-invariant mode's shared-prefix decode): a
+        """The KV pools for a call, one cache per pool form (KVCache.frag_only, "paged" for the paged own-KV form of generate_list, "shared" for
+        the row-major + fragment form of the batch-invariant mode's shared-prefix decode and of generate_list(group_images=True), or
+        "paged+shared" for that call with paged_kv=True): a
         driver alternates calls that group their decode rows (the image questions) with calls that do not (a handful of rows), and each
         keeps its pools - and the decode graphs captured over them - across calls; a cache only grows."""
         # prefix slots are whole 64-key chunks (the fragment image); own slots only need whole 16-key groups: 92 own tokens take
         # 96 rows, not 128 (a quarter of the own pool, 26 GB at 768 questions)
         t_pre, t_own = (max(t_pre, 64) + 63) // 64 * 64, (max(t_own, 64) + 15) // 16 * 16
-        form = "paged" if n_pages else ("shared" if with_frag else frag_only)
+        form = ("paged+shared" if with_frag else "paged") if n_pages else ("shared" if with_frag else frag_only)
         cur = self._kvs.get(form)
         if cur is None or not cur.fits(n_pre, t_pre, n_own, t_own, frag_only, n_pages, max_pages, with_frag):
             self._kvs.pop(form, None)
@@ -1578,7 +1625,7 @@ class VddLlavaEngine:
                       temperature: Optional[float] = None, top_p: Optional[float] = None, top_k: Optional[int] = None,
                       max_new_tokens: int = 64, eos_token_id=None, pad_token_id: Optional[int] = None, cd_greedy: bool = False,
                       n_top: int = 0, seed: Optional[int] = None, sync_every: int = 8, admit_min: Optional[int] = None,
-                      paged_kv: bool = False, kv_page_budget: Optional[int] = None) -> GenerateOutput:
+                      paged_kv: bool = False, kv_page_budget: Optional[int] = None, group_images: bool = False) -> GenerateOutput:
         """The reference walks an arbitrarily long question list one generate() call at a time (llava_sampling.py:78-116: LLaVA-Bench, answers
         of 20 - 1,000 tokens; llava_calibrate.py:130).  generate() decodes ONE batch to its end - the last rows of a batch of open-ended
         answers run almost alone.  This call takes the whole list and keeps `in_flight` questions decoding: when questions have emitted EOS
@@ -1600,12 +1647,31 @@ class VddLlavaEngine:
         worst case and what the device holds, or `kv_page_budget` pages; below the worst case a question can be preempted - taken out,
         its answer so far discarded, prefilled again later (stats['preemptions']) - so the call cannot deadlock.  Same answers in a
         deterministic decode; a sampled decode draws a preempted question afresh (still reproducible for a seed: the schedule depends
-        only on the polled finished flags).  in_flight is then only lowered when not even the staging pool + one question fit."""
+        only on the polled finished flags).  in_flight is then only lowered when not even the staging pool + one question fit.
+        group_images=True: the decode rows that share a prefix slot - the questions about one image, the image-free rows behind one system
+        prompt - attend it once per group on the matrix cores, as in generate(): the prefixes keep a fragment image beside their row-major
+        form (built at admission, for the new prefix slots), and the captured step reads group tables of fixed capacity that are
+        rebuilt from the host's state whenever rows are admitted, released, preempted or the step shrinks, and at every poll without
+        the rows that have finished (ops.list_prefix_work; stats['n_groups'] / ['shared_rows']: the peak number of groups with a live
+        row / of rows in groups).  Tuned mode: the arithmetic of the grouped pass (not the per-row bits; same seed, same answers),
+        with or without paged_kv.  Under ops.batch_invariant(shared_prefix=True) the call is accepted only with this keyword and
+        groups canonical prefixes alone (image prefixes, declared embeds_prefix): every answer equals generate()'s under the flag,
+        bit for bit; paged_kv is refused there, and so is the keyword under batch_invariant() without shared_prefix."""
         dev, lm = self.device, self.cfg.lm
-        if ops.invariant_shared_prefix():
+        group_images = bool(group_images)
+        inv_list = group_images and ops.invariant_shared_prefix()
+        if group_images and ops.GEMM_BATCH_INVARIANT and not inv_list:
+            raise ValueError("generate_list(group_images=True): the batch-invariant mode has no groups without its shared-prefix form; "
+                             "use ops.batch_invariant(shared_prefix=True) or leave group_images off")
+        if group_images and not self.group_attention:
+            raise ValueError("generate_list(group_images=True): this engine has group_attention off; turn it on or leave group_images off")
+        if inv_list and paged_kv:
+            raise ValueError("generate_list(group_images=True, paged_kv=True): the shared-prefix form of the batch-invariant mode has no paged "
+                             "own-KV form; leave paged_kv off under ops.batch_invariant(shared_prefix=True)")
+        if ops.invariant_shared_prefix() and not group_images:
             # this call never groups: its image rows would take the per-row arithmetic and no longer equal generate()'s under the flag
             raise ValueError("generate_list has no shared-prefix form: leave ops.INVARIANT_SHARED_PREFIX (batch_invariant(shared_prefix=True), "
-                             "--invariant-shared-prefix) off for it, or use generate()")
+                             "--invariant-shared-prefix) off for it, or use generate() (group_images=True is the list form that groups)")
         if eos_token_id is None:
             raise ValueError("generate_list needs eos_token_id: without an EOS every answer has max_new_tokens tokens and generate() in batches does the same work")
         if pad_token_id is None:
@@ -1683,25 +1749,55 @@ class VddLlavaEngine:
             raise ValueError("generate_list: kv_page_budget sizes the page pool of paged_kv=True")
         if paged_kv:
             Qc, n_pages = self._fit_paged(Qc, lambda q_: (pre_slots(q_), t_pool, nb * q_, suffix_cap), nb, pages_for(suffix_cap + max_new_tokens),
-                                          kv_page_budget)
+                                          kv_page_budget, with_frag=group_images)
         else:
-            Qc = self._fit_in_flight(Qc, lambda q_: (pre_slots(q_), t_pool, nb * q_, suffix_cap + max_new_tokens))
+            Qc = self._fit_in_flight(Qc, lambda q_: (pre_slots(q_), t_pool, nb * q_, suffix_cap + max_new_tokens), with_frag=group_images)
+        list_groups = None
+        if group_images:
+            # chunks per work item: fixed for the call (it sizes the partial layout that the captured launch bakes in) - the invariant
+            # mode's constant, else what generate() would pick for the first admission wave, a function of the list and in_flight alone
+            def prefix_of(i, nm):
+                if emb_mode:
+                    return emb_pre[i]
+                return (("img", tuple(ids_all[i][:s_img[i]]), id(images[i])), s_img[i] + n_img_tok) if nm == "main" else \
+                       ((nm, tuple(ids_all[i][:s_img[i]])), len(slot_cut(nm, ids_all[i], s_img[i])[0]))
+            if inv_list:
+                cpi = ops.INVARIANT_PREFIX_CHUNKS
+            else:
+                wave = {}
+                for nm in names:
+                    for i in range(Qc):
+                        key, P = prefix_of(i, nm)
+                        if key is not None and P > 0:
+                            wave[(nm, key)] = (wave.get((nm, key), (0, P))[0] + 1, P)
+                cpi = ops.prefix_chunks_per_item([[0, n_, 0, P] for n_, P in wave.values()], lm.n_heads)
+            # the bound of the work list for the call: every row a group of its own behind the longest prefix the pools hold
+            per_row = -(-((max(t_pool, 64) + 63) // 64 * 64) // (64 * cpi))
+            fitted = Qc
+            while nb * Qc * per_row > ops.PREFIX_LIST_MAX_ITEMS and Qc > 8:
+                Qc = max(8, Qc * 7 // 8)
+            if paged_kv and Qc != fitted:       # the page pool of the number in flight really used
+                Qc, n_pages = self._fit_paged(Qc, lambda q_: (pre_slots(q_), t_pool, nb * q_, suffix_cap), nb, pages_for(suffix_cap + max_new_tokens),
+                                              kv_page_budget, with_frag=True)
+            list_groups = dict(cpi=cpi, items_capacity=min(ops.PREFIX_LIST_MAX_ITEMS, nb * Qc * per_row), invariant=bool(inv_list))
         admit_min = min(admit_min, max(1, Qc // 2))
         n_pre = pre_slots(Qc)
         if paged_kv:
             pager = ListPager(n_pages, Qc, nb, suffix_cap, max_new_tokens, sync_every)
-            kv = self.kv(n_pre, t_pool, nb * Qc, suffix_cap, n_pages=n_pages, max_pages=pager.max_pages)
+            kv = self.kv(n_pre, t_pool, nb * Qc, suffix_cap, n_pages=n_pages, max_pages=pager.max_pages, with_frag=group_images)
             pager.alloc.pad_table(kv.n_own, kv.max_pages)        # a cache that grew in an earlier call: the device table has its shape
         else:
             pager = None
-            kv = self.kv(n_pre, t_pool, nb * Qc, suffix_cap + max_new_tokens, frag_only=False)
+            kv = self.kv(n_pre, t_pool, nb * Qc, suffix_cap + max_new_tokens, frag_only=False, with_frag=group_images)
         self._forget_kept_prefill(kv)
         eos_t = h2d_long(dev, eos_token_id)
         ctr0 = self._philox_counter(seed)
         cfgkey = ("list", Qc, nb, max_new_tokens, alpha, beta, warp.t, warp.k, warp.p, use_dd, use_dd_unk, vcd, cd_greedy, tuple(eos_token_id), pad_token_id,
                   ops.GEMM_BATCH_INVARIANT, ops.W8_DECODE) + (("paged",) if paged_kv else ())
+        if group_images:
+            cfgkey = cfgkey + (("group_images", list_groups["cpi"], list_groups["items_capacity"], list_groups["invariant"]),)
         tail = dict(alpha=alpha, beta=beta, warp=warp, contrast=contrast, is_vcd=vcd, both=(use_dd and use_dd_unk), greedy=cd_greedy, eos_t=eos_t,
-                    pad=pad_token_id, output_scores=False, n_groups=0, n_items=0, cpi=1, proc={}, admit=True)
+                    pad=pad_token_id, output_scores=False, n_groups=0, n_items=0, cpi=1, proc={}, admit=True, list_groups=list_groups)
         run = self._runner(cfgkey, Qc, nb, max_new_tokens, tail, kv)
         run.reset(ctr0)
         run.unfinished.zero_()                                   # every slot starts free
@@ -1723,6 +1819,8 @@ class VddLlavaEngine:
         slot_own = list(range(Qc))                               # own-slot id of branch 0 of each slot of the running step (the tail shrink drops slots)
         suffix_len = [int(e.shape[0]) - p_[1] for e, p_ in zip(emb_all, emb_pre)] if emb_mode else [len(r) - si - 1 for r, si in zip(ids_all, s_img)]
         slot_keys: List[list] = [[] for _ in range(Qc)]
+        slot_pre: List[list] = [[] for _ in range(Qc)]           # group_images: per branch (prefix slot, prefix length, row kind) of the question in each slot
+        peak_groups = peak_shared = 0
         feat_of: Dict[int, torch.Tensor] = {}
         waiting = list(range(N))
         stats = {"n_rows": nb * Qc, "questions": N, "in_flight": Qc, "in_flight_asked": asked, "admissions": 0, "prefill_tokens": 0, "steps": 0, "graph": False}
@@ -1733,6 +1831,21 @@ class VddLlavaEngine:
             if pager.alloc.dirty:
                 kv.page_table.copy_(h2d_int32(dev, pager.alloc.table)[0])
                 pager.alloc.dirty = False
+
+        def regroup(unf_h=None):
+            """group_images: the group tables of the running step from the host's state - the rows of the questions in flight, without
+            those the last poll found finished"""
+            nonlocal peak_groups, peak_shared
+            Qr = run.Q
+            rows_h, live, mode = [[0, 1, 0, 0] for _ in range(nb * Qr)], [False] * (nb * Qr), [0] * (nb * Qr)
+            for q in range(Qr):
+                if slot_q[q] < 0:
+                    continue
+                for b, (ps, P, kind) in enumerate(slot_pre[q]):
+                    r_ = b * Qr + q
+                    rows_h[r_], live[r_], mode[r_] = [0, P + 1, ps, P], unf_h is None or bool(unf_h[q]), kind
+            n_g, n_r = run.load_groups(rows_h, live, mode if inv_list else None)
+            peak_groups, peak_shared = max(peak_groups, n_g), max(peak_shared, n_r)
 
         def release(slots, keep_tokens):
             """slots leave the batch: finished (their tokens go to `master`) or preempted; their prefixes lose a reference"""
@@ -1749,7 +1862,7 @@ class VddLlavaEngine:
                         free_pre.append(e["slot"])
                         del table[key]
                 im = None if emb_mode else id(images[slot_q[q]])
-                slot_q[q], slot_keys[q] = -1, []
+                slot_q[q], slot_keys[q], slot_pre[q] = -1, [], []
                 if im is not None and not any(k_[0] == "img" and k_[2] == im for k_ in table):
                     feat_of.pop(im, None)
                 if paged_kv:
@@ -1784,11 +1897,13 @@ class VddLlavaEngine:
                         e = table.get(key)
                         if e is None:
                             e = table[key] = dict(slot=free_pre.pop(), ref=0, T=P)
-                            new_pre.append(dict(pre, slot=e["slot"], T=P, pos0=0, pslot=0, plen=0))
+                            new_pre.append(dict(pre, slot=e["slot"], T=P, pos0=0, pslot=0, plen=0, canonical=key[0] in ("img", "emb")))
                         e["ref"] += 1
                         slot_keys[q].append(key)
                         pslot = e["slot"]
                     suffix.append(dict(own, slot=row, pos0=P, pslot=pslot, plen=P))
+                    # (row kind of the invariant form: 1 behind a canonical prefix - an image prefix, a declared embeds_prefix)
+                    slot_pre[q].append((pslot, P if key is not None else 0, int(key is not None and key[0] in ("img", "emb"))))
                     dec.append((P + own["T"], own["T"], [row, P + own["T"] + 1, pslot, P]))
             for q, i in zip(slots, qs):
                 slot_q[q] = i
@@ -1807,7 +1922,13 @@ class VddLlavaEngine:
                         cd_seq.append(dict(slot=sl, tokens=pre, img=f, suf=suf, T=len(pre) + n_img_tok + len(suf), pos0=0, pslot=0, plen=0))
                 passes.append(self._prefill_pass(cd_seq, to_prefix_pool=True, last=True))
             passes.append(self._prefill_pass(suffix, to_prefix_pool=False, last=True, packs=True))
-            outs = self.lm.prefill(passes, kv)
+            frag_plen = None
+            if group_images and new_pre:        # fragment images of the NEW prefix slots (invariant form: the canonical ones); length 0
+                fl = [0] * kv.kp[0].shape[0]    # elsewhere - slots in use keep theirs, the cd scratch slots need none
+                for p_ in new_pre:
+                    fl[p_["slot"]] = p_["T"] if (not inv_list or p_.get("canonical")) else 0
+                (frag_plen,) = h2d_int32(dev, fl)
+            outs = self.lm.prefill(passes, kv, frag_plen=frag_plen)
             if paged_kv:                        # the suffixes' K / V: staging slots -> the pages the rows were just given
                 sync_page_table()
                 sl_, nt_ = h2d_int32(dev, [s_["slot"] for s_ in suffix], [s_["T"] for s_ in suffix])
@@ -1847,11 +1968,17 @@ class VddLlavaEngine:
             e0.record(torch.cuda.current_stream(dev))
             t0 = _time.perf_counter()
             admit(slots)
+            if group_images:
+                if last_unf is not None:
+                    for q in slots:
+                        last_unf[q] = 1     # (a first token that was EOS shows at the next poll)
+                regroup(last_unf)
             host_admit += _time.perf_counter() - t0
             e1.record(torch.cuda.current_stream(dev))
             ev_pairs.append((e0, e1))
 
         steps, marks = 0, []
+        last_unf = None                     # the finished flags of the last poll (slots admitted since count as live)
         if paged_kv:
             sync_page_table()
             timed_admit(list(range(pager.n_admissible(0, [suffix_len[i] for i in waiting[:Qc]]))))
@@ -1870,6 +1997,12 @@ class VddLlavaEngine:
             Qr = run.Q
             done = [q for q in range(Qr) if not unf_h[q] and slot_q[q] >= 0]
             preempted = []
+            if group_images:
+                # rows that have finished leave their groups here, whether or not a waiting question takes the slot in this poll: prefix
+                # bytes follow the live rows at poll granularity (an admission, a preemption or a tail shrink below rebuilds the tables again)
+                last_unf = list(unf_h)
+                if done:
+                    regroup(last_unf)
             if paged_kv:
                 # finished questions give their pages back at once; every live row gets the pages the steps up to the next poll can write -
                 # and when the pool cannot cover that, the most recently admitted questions go back to the head of the waiting list
@@ -1883,6 +2016,9 @@ class VddLlavaEngine:
                     release(preempted, False)
                     for q in preempted:
                         unf_h[q] = 0
+                    if group_images:
+                        last_unf = list(unf_h)
+                        regroup(last_unf)
                 sync_page_table()
             if not waiting:
                 if not any(unf_h):
@@ -1895,7 +2031,11 @@ class VddLlavaEngine:
                     small = self._runner(cfgkey + ("tail", len(live)), len(live), nb, max_new_tokens, tail, kv)
                     small.adopt_slots(run, torch.tensor(live, dtype=torch.long, device=dev))
                     slot_q, slot_keys, slot_own = [slot_q[q] for q in live], [slot_keys[q] for q in live], [slot_own[q] for q in live]
+                    slot_pre = [slot_pre[q] for q in live]
                     run = small
+                    if group_images:
+                        last_unf = [1] * len(live)
+                        regroup(last_unf)
                     stats["tail_shrinks"] = stats.get("tail_shrinks", 0) + 1
                 continue
             free = [q for q in range(Qr) if not unf_h[q]]
@@ -1913,23 +2053,26 @@ class VddLlavaEngine:
         gen = gen.clone()
         seqs_out = prompt_plus_answer(dev, ids_all, gen)        # (embedding prompts: ids_all is empty per question - the new tokens alone)
         stats.update(steps=steps, graph=run.graph is not None, answer_tokens=int(done_at.sum().item()) + N,
-                     mean_live_rows=round(live_row_steps / max(steps, 1), 1), n_groups=0, paged_kv=bool(paged_kv),
+                     mean_live_rows=round(live_row_steps / max(steps, 1), 1), n_groups=peak_groups, paged_kv=bool(paged_kv),
                      own_kv_bytes=2 * sum(t_.numel() * t_.element_size() for t_ in ((kv.pk + kv.ko) if paged_kv else kv.ko)))
         if paged_kv:
             stats.update(pager.stats())
+        if group_images:
+            stats.update(group_images=True, shared_rows=peak_shared, prefix_chunks_per_item=list_groups["cpi"],
+                         items_capacity=list_groups["items_capacity"])
         return GenerateOutput(seqs_out, gen, None, top_prob, top_tok, stats)
 
     share_repeated_rows = True        # _plan: image-free rows with identical ids share all but their last position
     REPEATED_ROWS_MIN_SAVED = 256     # ... when that saves at least this many prefill tokens in a branch (every distinct row takes a prefix slot)
     KV_MEMORY_FRACTION = 0.92     # of what is free (+ what the pools being replaced give back): the rest is prefill activations, logits, graphs
 
-    def _fit_in_flight(self, Qc: int, dims) -> int:
+    def _fit_in_flight(self, Qc: int, dims, with_frag: bool = False) -> int:
         """generate_list holds its own-KV slots at full length (suffix + max_new_tokens) for the whole call: 90 questions x 3 branches x 1,024
         new tokens of a 13B model are 228 GB.  The number in flight is lowered (by eighths, not below 8) until the pools `dims(Qc)` =
         (n_pre, t_pre, n_own, t_own) fit the device; the caller sees the value used in stats['in_flight']."""
         if self.device.type != "cuda":
             return Qc
-        cur = self._kvs.get(False)
+        cur = self._kvs.get("shared" if with_frag else False)      # (with_frag: the fragment images beside the row-major prefixes count)
         free, _total = torch.cuda.mem_get_info(self.device)
         avail = free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device) + (cur.nbytes() if cur is not None else 0)
 
@@ -1938,15 +2081,15 @@ class VddLlavaEngine:
             t_pre, t_own = (max(t_pre, 64) + 63) // 64 * 64, (max(t_own, 64) + 15) // 16 * 16
             if cur is not None:
                 n_pre, t_pre, n_own, t_own = max(n_pre, cur.n_pre), max(t_pre, cur.t_pre), max(n_own, cur.n_own), max(t_own, cur.t_own)
-            return KVCache.bytes_needed(self.cfg.lm, n_pre, t_pre, n_own, t_own, self.dtype, False)
+            return KVCache.bytes_needed(self.cfg.lm, n_pre, t_pre, n_own, t_own, self.dtype, False, with_frag=with_frag)
         def fits_current(q_):
             n_pre, t_pre, n_own, t_own = dims(q_)
-            return cur is not None and cur.fits(n_pre, (max(t_pre, 64) + 63) // 64 * 64, n_own, (max(t_own, 64) + 15) // 16 * 16, False)
+            return cur is not None and cur.fits(n_pre, (max(t_pre, 64) + 63) // 64 * 64, n_own, (max(t_own, 64) + 15) // 16 * 16, False, with_frag=with_frag)
         while Qc > 8 and not fits_current(Qc) and need(Qc) > self.KV_MEMORY_FRACTION * avail:
             Qc = max(8, Qc * 7 // 8)
         return Qc
 
-    def _fit_paged(self, Qc: int, dims, nb: int, max_pages: int, budget: Optional[int]):
+    def _fit_paged(self, Qc: int, dims, nb: int, max_pages: int, budget: Optional[int], with_frag: bool = False):
         """generate_list(paged_kv=True) -> (questions in flight, pages of the pool).  The paged form costs prefix pools + staging pool
         `dims(Qc)` + page pool; the page pool is `budget` pages when given (ListPager refuses one that cannot hold a question at full
         length), else the smaller of the worst case - every slot at full length - and what KV_MEMORY_FRACTION of the free memory leaves.
@@ -1958,7 +2101,7 @@ class VddLlavaEngine:
             return Qc, int(budget)
         if self.device.type != "cuda":
             return Qc, worst(Qc)
-        cur = self._kvs.get("paged")
+        cur = self._kvs.get("paged+shared" if with_frag else "paged")
         free, _total = torch.cuda.mem_get_info(self.device)
         avail = free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device) + (cur.nbytes() if cur is not None else 0)
         page_bytes = KVCache.bytes_needed(lm, 0, 0, 0, 0, self.dtype, False, n_pages=1)
@@ -1968,7 +2111,7 @@ class VddLlavaEngine:
             t_pre, t_own = (max(t_pre, 64) + 63) // 64 * 64, (max(t_own, 64) + 15) // 16 * 16
             if cur is not None:
                 n_pre, t_pre, n_own, t_own = max(n_pre, cur.n_pre), max(t_pre, cur.t_pre), max(n_own, cur.n_own), max(t_own, cur.t_own)
-            rest = KVCache.bytes_needed(lm, n_pre, t_pre, n_own, t_own, self.dtype, False)
+            rest = KVCache.bytes_needed(lm, n_pre, t_pre, n_own, t_own, self.dtype, False, with_frag=with_frag)
             return int((self.KV_MEMORY_FRACTION * avail - rest) // page_bytes)
         while Qc > 8 and room(Qc) < floor(Qc):
             Qc = max(8, Qc * 7 // 8)

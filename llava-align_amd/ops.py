@@ -27,6 +27,8 @@ _SIGS = {
     "vdd_prefix_fragments": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vdd_decode_attention_grouped": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _L, _I, _L, _I, _I, _I, _I, _F, _I, _P],
     "vdd_decode_attention_shared_invariant": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _L, _I, _L, _I, _I, _I, _I, _I, _F, _I, _P],
+    "vdd_decode_attention_grouped_list": [_P] * 12 + [_I, _P, _P, _I, _I, _I, _I, _L, _I, _I, _I, _I, _L, _I, _I, _I, _I, _F, _I, _P],
+    "vdd_decode_attention_shared_invariant_list": [_P] * 12 + [_I, _P, _P, _I, _I, _I, _I, _L, _I, _L, _I, _I, _I, _I, _I, _F, _I, _P],
     "vdd_flash_attention": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _L, _I, _F, _I, _I, _P],
     "vdd_flash_attention_packed": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _L, _I, _F, _I, _P],
     "vdd_layernorm": [_P, _P, _P, _P, _I, _I, _F, _I, _P],
@@ -1329,17 +1331,7 @@ def invariant_prefix_work(rows, row_mode, chunks_per_item=None):
     ONE size chunks_per_item (default INVARIANT_PREFIX_CHUNKS) whatever the batch: sum over groups of ceil(n_rows / 16) *
     ceil(plen / (64 * chunks_per_item)) of them, longest first (order cannot matter: a partial depends on its own row alone)."""
     cpi = INVARIANT_PREFIX_CHUNKS if chunks_per_item is None else int(chunks_per_item)
-    if cpi < 1:
-        raise ValueError("chunks_per_item must be >= 1")
-    by = {}
-    for i, ((_, _, ps, pl), m) in enumerate(zip(rows, row_mode)):
-        if m and pl > 0:
-            by.setdefault((int(ps), int(pl)), []).append(i)
-    groups, members = [], []
-    for (ps, pl), idx in by.items():
-        groups.append([len(members), len(idx), ps, pl])
-        members += idx
-    return groups, members, prefix_work_items(groups, cpi)
+    return list_prefix_work(rows, [True] * len(rows), row_mode, cpi, float("inf"))[:3]     # every row live, no capacity
 
 
 def decode_attention_shared_invariant(q, k_cache, v_cache, k_prefix, v_prefix, rows, row_mode, groups, group_rows, items, n_items, H, Hkv, D,
@@ -1370,6 +1362,116 @@ def decode_attention_shared_invariant(q, k_cache, v_cache, k_prefix, v_prefix, r
         group_rows.data_ptr(), items.data_ptr(), int(n_items), out.data_ptr(), ws.data_ptr(), M, H, Hkv, D, k_cache.stride(0),
         k_cache.shape[2], k_prefix.stride(0), k_prefix.shape[2], int(max_prefix_len), int(max_own_len), int(max_row_len), cpi,
         D ** -0.5 if scale is None else scale, dt, _st(q)))
+    return out
+
+
+PREFIX_LIST_MAX_ITEMS = 65535    # what the list entries take as items_capacity at the most (a launch dimension's limit, as for n_items)
+
+
+def list_prefix_work(rows, live, row_mode=None, cpi=1, items_capacity=PREFIX_LIST_MAX_ITEMS):
+    """Host side of decode_attention_grouped_list / decode_attention_shared_invariant_list: the rows of a running list
+    [[slot, len, pslot, plen], ...], a live mask (finished, free and preempted rows: False) and, for the invariant form, row_mode
+    (1 = shared; None: every row behind a prefix is shared) -> (groups [[row_off, n_rows, pslot, plen]], group_rows, items
+    [[group, first_row, item, 0]], n_items).  Every live shared row with plen > 0 is in exactly one group, the rows with its
+    (pslot, plen) in row order, groups in order of their first row; every other row is in none, and a prefix nobody live reads has
+    no group.  Items as prefix_work_items: sum over groups of ceil(n_rows / 16) * ceil(plen / (64 cpi)), longest first.  A function of
+    its arguments alone.  Raises ValueError when the items do not fit items_capacity."""
+    cpi = int(cpi)
+    if cpi < 1:
+        raise ValueError("chunks_per_item must be >= 1")
+    if len(live) != len(rows) or (row_mode is not None and len(row_mode) != len(rows)):
+        raise ValueError("list_prefix_work: one live flag (and one row_mode) per row")
+    by = {}
+    for i, (_, _, ps, pl) in enumerate(rows):
+        if live[i] and pl > 0 and (row_mode is None or row_mode[i]):
+            by.setdefault((int(ps), int(pl)), []).append(i)
+    groups, members = [], []
+    for (ps, pl), idx in by.items():
+        groups.append([len(members), len(idx), ps, pl])
+        members += idx
+    items = prefix_work_items(groups, cpi)
+    if len(items) > items_capacity:
+        raise ValueError(f"list_prefix_work: {len(items)} work items exceed the capacity of the call ({items_capacity})")
+    return groups, members, items, len(items)
+
+
+def _list_tables_ok(M, groups, group_rows, items, n_items_dev, items_capacity):
+    """the device tables of a list entry can hold what the kernels may index: items_capacity item records, one int32 count, and - every
+    one of the M rows a group of its own at the most - M group records and M member rows"""
+    cap = int(items_capacity)
+    for t in (groups, group_rows, items, n_items_dev):
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("list attention: groups, group_rows, items and n_items_dev are contiguous int32 device tensors")
+    if items.numel() < 4 * max(cap, 1) or n_items_dev.numel() < 1:
+        raise ValueError("list attention: `items` holds fewer than items_capacity records")
+    if groups.numel() < 4 * M or group_rows.numel() < M:
+        raise ValueError("list attention: `groups` / `group_rows` hold fewer than one record per row")
+    return cap
+
+
+def decode_attention_grouped_list(q, k_cache, v_cache, k_prefix, v_prefix, rows, groups, group_rows, items, n_items_dev, items_capacity,
+                                  H, Hkv, D, max_prefix_len, max_own_len, prefix_frag, out=None, workspace=None, chunks_per_item=1, scale=None,
+                                  page_table=None):
+    """decode_attention_grouped for a work list that changes under ONE captured launch: groups / group_rows / items are device tables
+    of fixed capacity (items: items_capacity records) that the host rewrites between replays (list_prefix_work), n_items_dev the int32
+    device count the prefix pass reads.  Bit-identical to decode_attention_grouped on equal tables.  page_table: k_cache / v_cache
+    are the page pools [n_pages, Hkv, PAGE, D] of the paged own-KV form, own keys read through the table - bit-identical to the
+    contiguous form over the same K / V."""
+    dt = _dt(q, k_cache, v_cache, k_prefix, v_prefix)
+    M = q.shape[0]
+    lib = _lib_ready()
+    cap = _list_tables_ok(M, groups, group_rows, items, n_items_dev, items_capacity)
+    r64 = lambda v: (int(v) + 63) // 64 * 64
+    lib.vdd_decode_attention_workspace_bytes.restype = C.c_int64
+    need = lib.vdd_decode_attention_workspace_bytes(M, H, D, r64(max_prefix_len) + r64(max_own_len))
+    ws = workspace if workspace is not None else _attn_ws.get((q.device,))
+    if ws is None or ws.numel() * 4 < need:
+        if workspace is not None:
+            raise ValueError("attention workspace too small")
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=q.device)
+        _attn_ws[(q.device,)] = ws
+    out = torch.empty_like(q) if out is None else out
+    if page_table is not None:
+        stride, *pool = _page_pool(k_cache, v_cache, page_table)
+        t_max = 0
+    else:
+        stride, t_max, pool = k_cache.stride(0), k_cache.shape[2], (0, 0, 0)
+    _lib.check(lib.vdd_decode_attention_grouped_list(
+        q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), page_table.data_ptr() if page_table is not None else None, k_prefix.data_ptr(),
+        v_prefix.data_ptr(), prefix_frag.data_ptr() if prefix_frag is not None else None, rows.data_ptr(), groups.data_ptr(),
+        group_rows.data_ptr(), items.data_ptr(), n_items_dev.data_ptr(), cap, out.data_ptr(), ws.data_ptr(), M, H, Hkv, D, stride, t_max,
+        *pool, k_prefix.stride(0), k_prefix.shape[2], int(max_prefix_len), int(max_own_len), int(chunks_per_item),
+        D ** -0.5 if scale is None else scale, dt, _st(q)))
+    return out
+
+
+def decode_attention_shared_invariant_list(q, k_cache, v_cache, k_prefix, v_prefix, rows, row_mode, groups, group_rows, items, n_items_dev,
+                                           items_capacity, H, Hkv, D, max_prefix_len, max_own_len, max_row_len, prefix_frag, out=None,
+                                           workspace=None, chunks_per_item=None, scale=None):
+    """decode_attention_shared_invariant for a work list that changes under ONE captured launch (tables as in
+    decode_attention_grouped_list; row_mode is rewritten with them).  Bit-identical to decode_attention_shared_invariant on equal
+    tables - so a row's output is still a function of its own q, keys, len and prefix_len alone.  Contiguous own pool only."""
+    dt = _dt(q, k_cache, v_cache, k_prefix, v_prefix)
+    M = q.shape[0]
+    lib = _lib_ready()
+    cap = _list_tables_ok(M, groups, group_rows, items, n_items_dev, items_capacity)
+    r64 = lambda v: (int(v) + 63) // 64 * 64
+    lib.vdd_decode_attention_workspace_bytes.restype = C.c_int64
+    need = lib.vdd_decode_attention_workspace_bytes(M, H, D, max(r64(max_prefix_len) + r64(max_own_len), r64(max_row_len)))
+    ws = workspace if workspace is not None else _attn_ws.get((q.device,))
+    if ws is None or ws.numel() * 4 < need:
+        if workspace is not None:
+            raise ValueError("attention workspace too small")
+        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=q.device)
+        _attn_ws[(q.device,)] = ws
+    out = torch.empty_like(q) if out is None else out
+    cpi = INVARIANT_PREFIX_CHUNKS if chunks_per_item is None else int(chunks_per_item)
+    _lib.check(lib.vdd_decode_attention_shared_invariant_list(
+        q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_prefix.data_ptr(), v_prefix.data_ptr(),
+        prefix_frag.data_ptr() if prefix_frag is not None else None, rows.data_ptr(), row_mode.data_ptr(), groups.data_ptr(),
+        group_rows.data_ptr(), items.data_ptr(), n_items_dev.data_ptr(), cap, out.data_ptr(), ws.data_ptr(), M, H, Hkv, D,
+        k_cache.stride(0), k_cache.shape[2], k_prefix.stride(0), k_prefix.shape[2], int(max_prefix_len), int(max_own_len), int(max_row_len),
+        cpi, D ** -0.5 if scale is None else scale, dt, _st(q)))
     return out
 
 

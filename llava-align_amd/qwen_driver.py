@@ -63,7 +63,7 @@ def run_qwen_pope(engine: VddLlavaEngine, questions: Sequence[dict], embed_promp
                   answers_path: Optional[str] = None, model_id: str = "qwen-vl", batch_questions: int = 128, eos_token_id=151643,
                   pad_token_id: Optional[int] = 151643, max_new_tokens: int = 20, min_new_tokens: Optional[int] = 1, use_cd: bool = False,
                   noise_step: int = 500, priors: Sequence[str] = PRIORS, prompt_format: str = POPE_PROMPT, rank: Optional[int] = None,
-                  world: Optional[int] = None, batch_invariant: Optional[bool] = None, invariant_shared_prefix: bool = False, sweep: Optional[Sequence[dict]] = None, paged_kv: bool = False,
+                  world: Optional[int] = None, batch_invariant: Optional[bool] = None, invariant_shared_prefix: bool = False, sweep: Optional[Sequence[dict]] = None, paged_kv: bool = False, group_images: bool = False,
                   **generate_kw) -> dict:
     """questions: POPE json lines (question_id, image, text[, label]).  load_image(name) -> the [3, S, S] tensor the model's own
     `visual.image_transform` makes of the file (qwen_calibrate.py:100-101).  generate_kw: temperature, top_p, top_k, use_dd, use_dd_unk,
@@ -78,7 +78,10 @@ def run_qwen_pope(engine: VddLlavaEngine, questions: Sequence[dict], embed_promp
     {"tag", "temperature", "top_p", "top_k"[, "answers_path"]} decodes every setting from ONE prefill per batch (engine.generate(reuse_prefill=True);
     not with --use_cd, whose noise is drawn per call, and not for open-ended lists, which go through generate_list per setting).
     Returns {"runs": {tag: result}}.
-    paged_kv: the open-ended list call (generate_list) keeps its own KV in pages that follow the tokens really generated."""
+    paged_kv: the open-ended list call (generate_list) keeps its own KV in pages that follow the tokens really generated.
+    group_images: that call attends a shared (declared) prefix once per group of rows (generate_list(group_images=True)).  A deterministic
+    decode runs in batch-invariant mode, which has no groups without its shared-prefix form: there it needs invariant_shared_prefix=True
+    (--invariant-shared-prefix) as well, or the engine raises ValueError."""
     from .vcd_add_noise import add_diffusion_noise
     priors = tuple(priors)
     if any(p_ not in PRIORS for p_ in priors):
@@ -124,7 +127,7 @@ def run_qwen_pope(engine: VddLlavaEngine, questions: Sequence[dict], embed_promp
             emb, pre = _embeds(embed_prompt, texts, imgs, [("clean", q["image"]) for q in qs])
             if as_list:
                 out = engine.generate_list(None, inputs_embeds=emb, embeds_prefix=pre, in_flight=batch_questions, max_new_tokens=max_new_tokens, n_top=10,
-                                           eos_token_id=eos_token_id, pad_token_id=pad_token_id, paged_kv=paged_kv, **kw)
+                                           eos_token_id=eos_token_id, pad_token_id=pad_token_id, paged_kv=paged_kv, group_images=group_images, **kw)
                 all_rows[0].add(idx, out.tokens, [(out.top_tok, out.top_prob)])
                 list_stats = out.stats
                 continue
@@ -192,6 +195,8 @@ def _parser():
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--paged-kv", action="store_true", default=argparse.SUPPRESS, help="open-ended lists: paged own-KV pool (engine.generate_list(paged_kv=True))")
+    ap.add_argument("--group-images", action="store_true", default=argparse.SUPPRESS, help="open-ended lists: a shared prefix is attended once per group of rows (engine.generate_list(group_images=True)); a deterministic "
+                    "run (batch-invariant mode) also needs --invariant-shared-prefix, else the call raises")
     ap.add_argument("--native-visual", action="store_true", help="the ViT + resampler on the package's kernels (qwen_visual) instead of the model's module")
     return ap
 
@@ -225,7 +230,7 @@ def main(argv=None):
     pope = "POPE" in a.question_file
     common = dict(image_path=lambda f: os.path.join(a.image_folder, f), model_id="qwen-vl" if "Chat" not in a.model_path else "qwen-vl-chat",
                   batch_questions=a.batch, eos_token_id=tok.eod_id, pad_token_id=tok.eod_id, use_cd=a.use_cd, noise_step=a.noise_step, rank=rank, world=world,
-                  use_dd=a.use_dd, use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, seed=a.seed, paged_kv=getattr(a, "paged_kv", False), **mode_kw(a))
+                  use_dd=a.use_dd, use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, seed=a.seed, paged_kv=getattr(a, "paged_kv", False), group_images=getattr(a, "group_images", False), **mode_kw(a))
     if a.sampling and pope and len(runs) > 1:
         # the POPE sampling sweep (answers of <= 20 tokens): every setting from ONE pass over the question file, a batch's prefill shared by its settings
         sweep = [dict(tag=tag, temperature=temp, top_p=top_p, top_k=top_k, answers_path=os.path.expanduser(a.answers_file).replace("setting", tag))

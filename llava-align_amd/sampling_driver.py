@@ -33,7 +33,8 @@ def run_sampling(engine: VddLlavaEngine, questions: Sequence[dict], encode: Call
                  load_image: Callable[[str], torch.Tensor], answers_path: Optional[str] = None, model_id: str = "llava-align_amd",
                  pope_suffix: bool = False, in_flight: int = 90, max_new_tokens: int = 1024, eos_token_id=2, pad_token_id: Optional[int] = 0,
                  stop_str: Optional[str] = "</s>", noise_step: Optional[int] = None, rank: Optional[int] = None, world: Optional[int] = None,
-                 batch_invariant: Optional[bool] = None, invariant_shared_prefix: bool = False, paged_kv: bool = False, **generate_kw) -> dict:
+                 batch_invariant: Optional[bool] = None, invariant_shared_prefix: bool = False, paged_kv: bool = False, group_images: bool = False,
+                 **generate_kw) -> dict:
     """questions: dicts with question_id, image, text.  generate_kw: cd_alpha, cd_beta, use_dd, use_dd_unk, temperature, top_p, top_k, seed,
     cd_greedy - the reference's generate kwargs (llava_sampling.py:96-109; temperature 0 there means greedy: pass do_sample=False).
     rank / world (default: the initialised torch.distributed group): every rank decodes its contiguous chunk of whole images
@@ -41,6 +42,10 @@ def run_sampling(engine: VddLlavaEngine, questions: Sequence[dict], encode: Call
     run in batch-invariant mode unless told otherwise (shard.resolve_batch_invariant): same answers on 1 and N ranks, at any in_flight.
     paged_kv: engine.generate_list(paged_kv=True) - own-KV memory follows the tokens really generated, so `in_flight` questions fit at
     max_new_tokens=1024 where full-length slots would not.
+    group_images: engine.generate_list(group_images=True) - the questions about one image attend its prefix once per step (with
+    invariant_shared_prefix it is what lets the list call run under that flag at all).  A deterministic decode (cd_greedy, top_k = 1)
+    runs in batch-invariant mode, which has no groups without its shared-prefix form: there group_images needs
+    invariant_shared_prefix=True (--invariant-shared-prefix) as well, or the engine raises ValueError.
     Returns {"answers": [...], "stats": the engine's stats of this rank's chunk}."""
     run = ShardedRun(questions, rank, world, generate_kw, batch_invariant, invariant_shared_prefix)
     mine, generate_kw = run.mine, run.generate_kw
@@ -55,7 +60,7 @@ def run_sampling(engine: VddLlavaEngine, questions: Sequence[dict], encode: Call
             if noise_step is not None:
                 kw["images_cd"] = [add_diffusion_noise(im, noise_step) for im in imgs]                 # fresh noise per question (:88-91)
             out = engine.generate_list(ids, imgs, in_flight=in_flight, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                       paged_kv=paged_kv, **kw)
+                                       paged_kv=paged_kv, group_images=group_images, **kw)
             rows.add(mine, out.tokens)
             stats = out.stats
         elif mine:                  # do_sample=False: greedy_search is not patched - plain arg-max decoding, batch after batch
@@ -87,6 +92,8 @@ def _parser():
     ap.add_argument("--max_new_tokens", type=int, default=1024)
     ap.add_argument("--in-flight", type=int, default=90)
     ap.add_argument("--paged-kv", action="store_true", default=argparse.SUPPRESS, help="paged own-KV pool: memory follows the tokens really generated (engine.generate_list(paged_kv=True))")
+    ap.add_argument("--group-images", action="store_true", default=argparse.SUPPRESS, help="questions about one image attend its prefix once per step (engine.generate_list(group_images=True)); a deterministic run "
+                    "(batch-invariant mode) also needs --invariant-shared-prefix, else the call raises")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--naive", action="store_true", help="experiments/eval/llava_naive.py:39-98: ONE run at --temperature / --top_p / --top_k (greedy at "
                     "temperature 0), always with the one-word suffix, into --answers-file as given")
@@ -124,7 +131,7 @@ def main(argv=None):
                            lambda name: K.clip_preprocess(proc, os.path.join(a.image_folder, name)), answers_path=path,
                            model_id=os.path.basename(a.model_path.rstrip("/")), pope_suffix=a.naive or "POPE" in a.question_file, in_flight=a.in_flight,
                            max_new_tokens=a.max_new_tokens, eos_token_id=tok.eos_token_id, pad_token_id=tok.pad_token_id or 0,
-                           noise_step=a.noise_step if a.use_cd else None, rank=rank, world=world, paged_kv=getattr(a, "paged_kv", False), use_dd=a.use_dd,
+                           noise_step=a.noise_step if a.use_cd else None, rank=rank, world=world, paged_kv=getattr(a, "paged_kv", False), group_images=getattr(a, "group_images", False), use_dd=a.use_dd,
                            use_dd_unk=a.use_dd_unk, cd_alpha=a.cd_alpha, cd_beta=a.cd_beta, temperature=temp if temp > 0 else 1.0, top_p=top_p, top_k=top_k, seed=a.seed, **mode_kw(a), **greedy)
         if rank == 0:
             print(json.dumps({"run": tag or "naive", "answers_file": path, "n_answers": len(res["answers"]), "stats": {k: v for k, v in res["stats"].items() if not hasattr(v, "__len__") or isinstance(v, str)}}), flush=True)
