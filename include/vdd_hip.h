@@ -256,6 +256,18 @@ int vdd_gemm_w8(const void* X, const void* W8, const float* w_scale, void* Y, co
                 int epilogue, int config, void* workspace, int64_t workspace_bytes,
                 int dtype, void* hip_stream);
 
+/* The same GEMM for a weight that exists ONLY as 8-bit weight rows (load_8bit with w8_only: there is no w16 to fall back to): the
+ * signature, operands, `config` word, workspace and bit-for-bit contract of vdd_gemm_w8, on every tile id that has an 8-bit form -
+ * 1-16 without 5 (256 x 192: its 12 code images do not divide by its 8 waves).  Ids 7-16 launch the instantiations vdd_gemm_w8
+ * launches.  Ids 1-4 and 6 keep the two-buffer K pipeline of their 16-bit twins with 64-byte W rows (id 4 without its third W image);
+ * the bits do not depend on the pipeline.  Served: all three schedules, any M, K % 128 == 0, epilogues VDD_GEMM_NONE, _BIAS,
+ * _SWIGLU (ids 1-4, 8, 10-12, 15: where vdd_gemm pairs gate and up), slabs on tile 8.  Anything else - tile id 5, the GELU and
+ * bias + residual epilogues, K % 128 != 0 - returns VDD_ERR_UNSUPPORTED with nothing launched and nothing written. */
+int vdd_gemm_codes(const void* X, const void* W8, const float* w_scale, void* Y, const void* bias,
+                   int M, int N, int K, int64_t ldx, int64_t ldy,
+                   int epilogue, int config, void* workspace, int64_t workspace_bytes,
+                   int dtype, void* hip_stream);
+
 /* Row-batched projection GEMM, any M above the skinny regime (csrc/vdd_gemm.hip): Y[M,N] = epilogue(X[M,K] W[N,K]^T), bf16 in,
  * fp32 accumulate (32x32x16 MFMA, both operands LDS-DMA'd into swizzled LDS tiles, persistent stream-K over one workgroup
  * per CU), bf16 out.  K % 128 == 0, N % 4 == 0, ldx/ldw % 8 == 0 (elements).  Replaces the eager nn.Linear calls of HF

@@ -89,10 +89,11 @@ def load_tokenizer(path: str):
 
 
 def load_llava(model_path: str, device, dtype=torch.float16, vision_tower: Optional[str] = None, fallback_preset: Optional[str] = None,
-               use_graph: bool = True, load_8bit: bool = False, load_4bit: bool = False) -> Tuple[VddLlavaEngine, object, object]:
+               use_graph: bool = True, load_8bit: bool = False, load_4bit: bool = False, w8_only: bool = False) -> Tuple[VddLlavaEngine, object, object]:
     """-> (engine, tokenizer, CLIP image processor) of a LLaVA-1.5 checkpoint directory; dtype fp16 as the reference loads it (builder.py:40).
     load_8bit / load_4bit: the reference's `load_pretrained_model(..., load_8bit, load_4bit)` (builder.py:26-31) - see VddLlavaEngine: 8-bit is
-    e4m3 weight storage for the few-row decode step, 4-bit raises NotImplementedError."""
+    e4m3 weight storage for the few-row decode step, 4-bit raises NotImplementedError.  w8_only (with load_8bit): the quantised weights are
+    kept as codes only (VddLlavaEngine)."""
     from transformers import CLIPImageProcessor
     cfg = config_from_dir(model_path, vision_tower, fallback_preset)
     sd = load_state_dict(model_path)
@@ -105,7 +106,7 @@ def load_llava(model_path: str, device, dtype=torch.float16, vision_tower: Optio
             raise FileNotFoundError(f"the checkpoint holds no CLIP tower and its mm_vision_tower ({tower_dir!r}) is not a local directory: pass --vision-tower DIR")
         vision_sd = load_state_dict(tower_dir)
     w = LlavaWeights.from_state_dict(cfg, sd, device, vision_sd=vision_sd, dtype=dtype)
-    eng = VddLlavaEngine(cfg, weights=w, device=device, use_graph=use_graph, load_8bit=load_8bit, load_4bit=load_4bit)
+    eng = VddLlavaEngine(cfg, weights=w, device=device, use_graph=use_graph, load_8bit=load_8bit, load_4bit=load_4bit, w8_only=w8_only)
     proc_dir = next((d for d in (model_path, tower_dir) if d and os.path.exists(os.path.join(d, "preprocessor_config.json"))), None)
     if proc_dir is None:
         raise FileNotFoundError("no preprocessor_config.json (CLIPImageProcessor) in the checkpoint or the vision tower directory")
@@ -178,7 +179,7 @@ def qwen_embed_prompt(model, tokenize, device, keep_images: int = 16, tower=None
 
 
 def load_qwen(model_path: str, device, dtype=torch.bfloat16, use_graph: bool = True, native_visual: bool = False, load_8bit: bool = False,
-              load_4bit: bool = False):
+              load_4bit: bool = False, w8_only: bool = False):
     """-> (engine, tokenizer, HF model, embed_prompt) of a Qwen-VL directory, as the reference's drivers load it
     (`AutoTokenizer / QWenLMHeadModel.from_pretrained(model_path, trust_remote_code=True)`, MME/run_qwen.py:146-157, qwen_calibrate.py:75-86:
     the caller's environment must provide what modeling_qwen.py imports).  The language model runs natively (hf_adapter.lm_weights_from_hf);
@@ -188,7 +189,7 @@ def load_qwen(model_path: str, device, dtype=torch.bfloat16, use_graph: bool = T
     including </img>, which every prompt about the same image starts with.
     native_visual: the ViT + resampler run on the package's kernels instead (qwen_visual.QwenVisualTower over the model's own
     `transformer.visual` weights); embed_prompt then also offers `encode_batch(images)`, which the drivers call per batch.
-    load_8bit / load_4bit: as load_llava (the engine's language model; the HF model's own parameters stay as loaded)."""
+    load_8bit / load_4bit / w8_only: as load_llava (the engine's language model; the HF model's own parameters stay as loaded)."""
     if load_4bit:
         raise NotImplementedError("load_4bit: this package has no 4-bit weight form; load_8bit=True (e4m3 weight streaming) is the quantised option")
     from transformers import AutoModelForCausalLM, AutoTokenizer
@@ -198,7 +199,7 @@ def load_qwen(model_path: str, device, dtype=torch.bfloat16, use_graph: bool = T
     tok.pad_token_id = tok.eod_id
     model = AutoModelForCausalLM.from_pretrained(model_path, trust_remote_code=True, torch_dtype=dtype).to(device).eval()
     cfg = lm_config_from_hf(model)
-    eng = VddLlavaEngine(cfg, weights=lm_weights_from_hf(model, cfg), device=device, use_graph=use_graph, load_8bit=load_8bit)
+    eng = VddLlavaEngine(cfg, weights=lm_weights_from_hf(model, cfg), device=device, use_graph=use_graph, load_8bit=load_8bit, w8_only=w8_only)
     tower = None
     if native_visual:
         from .qwen_visual import QwenVisualTower, QwenVisualWeights

@@ -102,7 +102,12 @@ constexpr int gemm_stages(int BM, int BN, int WM, int WN) {
 // The 8-bit weight form of a W stream (vdd_gemm_w8): W reaches LDS as e4m3 codes, 64 B per row and K-tile instead of 128, so a K-tile
 // buffer is BM * 128 + BN * 64 bytes and the freed LDS goes to more buffers - as many as fit beside the staging blocks, at most eight,
 // and never more than the 6-bit vmcnt counts (XJ + BN / 16 / NW LDS-DMA instructions per wave and K-tile).
+// The compute-bound tiles (two buffers) keep two in their 8-bit form (vdd_gemm_codes: weights that exist as codes only): the halved W image
+// would buy 128 x 256 four buffers and 256 x 128 / 192 x 256 / 192 x 192 three, but the W-stream pipeline's run-time buffer indices cost
+// these tiles 5 - 36 spilled VGPRs where their 16-bit twins spill none (compiler report) - and they are MFMA-bound, not
+// bound by bytes in flight.
 constexpr int gemm_stages_w8(int BM, int BN, int WM, int WN) {
+    if (gemm_stages(BM, BN, WM, WN) == 2) return 2;       // the compute-bound tiles (vdd_gemm_codes): their two-buffer pipeline as it is
     const int n = (LDS_BYTES - gemm_staging_bytes(BN, WM, WN)) / (BM * 128 + BN * 64);
     const int cap = 63 / ((BM / 8 + BN / 16) / (WM * WN)) + 1;
     const int m = n > 8 ? 8 : n;
@@ -119,11 +124,13 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
     constexpr int WROW = W8 ? 64 : 128;                    // bytes of a W row in a K-tile buffer
     constexpr int BUF = BM * 128 + BN * WROW;              // bytes of one K-tile buffer
     constexpr int NSTG = W8 ? gemm_stages_w8(BM, BN, WM, WN) : gemm_stages(BM, BN, WM, WN);      // K-tile buffers (> 2: a W stream, see the K pipeline below)
-    static_assert(!W8 || (gemm_stages(BM, BN, WM, WN) >= 3 && NSTG >= 3), "the 8-bit weight form exists for the W-stream tiles only");
     constexpr int NMMA = NI * MI, NRD = NI + MI, NLD = XJ + WJ;
     // (the 192 x 256 tile of the decode batch only: down-projection 134 -> 120 us, o 57 -> 53 on cold weights; the 256 x 256 tile lost 5 - 12 % with it
     //  at 1,536 rows - 13 more spilled registers at the cliff - and gained nothing at prefill size, where the panels are L2 hits)
-    constexpr bool WAHEAD = NSTG == 2 && gemm_staging_bytes(BN, WM, WN) >= BN * 128 && BM == 192 && BN == 256;
+    constexpr bool WAHEAD = !W8 && NSTG == 2 && gemm_staging_bytes(BN, WM, WN) >= BN * 128 && BM == 192 && BN == 256;      // (its 8-bit form: the plain two-buffer pipeline)
+    // 8-bit form of the tiles whose accumulators take 96 registers or more (256 x 256, 192 x 256, 192 x 192): 8 bytes of codes per k-step
+    // instead of 16 per two - holding the second k-step pair's codes (wq) costs them their register budget (compiler report)
+    constexpr bool W8_READ8 = W8 && NSTG == 2 && NMMA >= 6;
     static_assert(XIMG % NW == 0 && WIMG % NW == 0 && TM % 32 == 0 && TN % 32 == 0, "tile / wave shape");
     static_assert(EPI != EPI_SWIGLU || NI % 2 == 0, "SwiGLU pairs gate/up 32-column blocks inside a wave");
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -306,7 +313,10 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
                 // set wg[kk + 2] is free (where the 16-bit form issues its read) and are widened there: no LDS read of W at k-steps 2 and 3
 #pragma unroll
                 for (int i = 0; i < NI; ++i) {
-                    if (kk < 2) {
+                    if constexpr (W8_READ8) {         // chunk 2 (kk % 2) + (lane >> 5): k-step kk in its low 8 bytes, kk + 2 in its high 8
+                        const uint2 c = *reinterpret_cast<const uint2*>(lds + buf * BUF + (((wrow + i * 2048) ^ ((kk & 1) << 5)) + (kk >> 1) * 8));
+                        wg[kk][i] = __builtin_bit_cast(frag8_t, w8_widen(c));
+                    } else if (kk < 2) {
                         const uint4 c = *reinterpret_cast<const uint4*>(lds + buf * BUF + ((wrow + i * 2048) ^ (kk << 5)));
                         wg[kk][i] = __builtin_bit_cast(frag8_t, w8_widen(make_uint2(c.x, c.y)));
                         wq[kk & 1][i] = make_uint2(c.z, c.w);
@@ -523,7 +533,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_kernel(const GemmArgs a) {
             // and one slab after the other is one memory round trip (~2 us) each: the finisher of such a tile spent 10 - 15 us here, most
             // of the launch.  So the loads of up to RU slabs go out together (32 - 64 registers each); they are ADDED in slab order as
             // before - the same bits.  (RU = 1 for the large tiles: a slab is 96 - 128 registers there, and a tile is cut in two.)
-            constexpr int PER = NI * MI * 16, RU = PER <= 32 ? 4 : PER <= 64 ? 3 : 1;
+            constexpr int PER = NI * MI * 16, RU = PER <= 32 ? 4 : PER <= 64 ? ((W8 && NSTG == 2) ? 1 : 3) : 1;      // (256 x 128 on codes: one at a time - 0 spilled VGPRs, as its twin; 3 cost it 34)
             auto load_slab = [&](int r, f32x4_t (&v)[NI * MI * 4]) {
                 const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)(a.partial + (size_t)r * (BM * BN)), 0, BM * BN * 4, 0x00020000);
 #pragma unroll
@@ -763,8 +773,9 @@ int launch_cfg(const GemmArgs& a0, int epi, int sched, void* workspace, int64_t 
         break;                                                                                                        \
     }
     if constexpr (W8) {
-        // the 8-bit weight form: W-stream tiles only (three or more K-tile buffers), epilogues NONE / BIAS / SWIGLU and the slabs of the 64 x 256 tile
-        if constexpr (gemm_stages(BM, BN, WM, WN) >= 3 && (BN / 16) % (WM * WN) == 0) {
+        // the 8-bit weight form: every tile whose codes images divide by its waves (not 256 x 192: 12 images, 8 waves), epilogues NONE / BIAS / SWIGLU
+        // and the slabs of the 64 x 256 tile (vdd_gemm_w8 itself keeps to the W-stream tiles, ids 7 - 16)
+        if constexpr ((BN / 16) % (WM * WN) == 0) {
             if (a.slab_S > 0) {
                 if constexpr (BM == 64 && BN == 256) { epi = EPI_SLABS; switch (epi) { VDD_GEMM_LAUNCH(EPI_SLABS) } }
                 else return VDD_ERR_UNSUPPORTED;
@@ -879,8 +890,9 @@ VDD_HIDDEN int VDD_IMPL(vdd_gemm)(const void* X, const void* W, void* Y, const v
     return dispatch_cfg<false>(config, a, epilogue, sched, workspace, workspace_bytes, st);
 }
 
-VDD_HIDDEN int VDD_IMPL(vdd_gemm_w8)(const void* X, const void* W8, const float* w_scale, void* Y, const void* bias, int M, int N, int K, int64_t ldx,
-             int64_t ldy, int epilogue, int config, void* workspace, int64_t workspace_bytes, void* stream) {
+// vdd_gemm_w8 (all_tiles = false: the W-stream tiles, ids 7 - 16) and vdd_gemm_codes (every tile id that has an 8-bit form)
+static int gemm_on_codes(bool all_tiles, const void* X, const void* W8, const float* w_scale, void* Y, const void* bias, int M, int N, int K, int64_t ldx,
+                  int64_t ldy, int epilogue, int config, void* workspace, int64_t workspace_bytes, void* stream) {
     if (M <= 0 || N <= 0) return VDD_OK;
     if (!X || !W8 || !w_scale || !Y || K <= 0 || (ldx % 8) || (ldy % 4) || N % 4 != 0 || ((uintptr_t)w_scale & 15)) return VDD_ERR_INVALID_ARG;
     // what this entry does not serve, before anything is launched: the caller runs vdd_gemm on w16
@@ -904,7 +916,19 @@ VDD_HIDDEN int VDD_IMPL(vdd_gemm_w8)(const void* X, const void* W8, const float*
     }
     config = (config & 15) | (((config >> 6) & 3) << 4);
     if (config == 0) config = 1;
+    if (!all_tiles && config < 7) return VDD_ERR_UNSUPPORTED;       // vdd_gemm_w8: the W-stream tiles only
     return dispatch_cfg<true>(config, a, epilogue, sched, workspace, workspace_bytes, st);
+}
+
+VDD_HIDDEN int VDD_IMPL(vdd_gemm_w8)(const void* X, const void* W8, const float* w_scale, void* Y, const void* bias, int M, int N, int K, int64_t ldx,
+             int64_t ldy, int epilogue, int config, void* workspace, int64_t workspace_bytes, void* stream) {
+    return gemm_on_codes(false, X, W8, w_scale, Y, bias, M, N, K, ldx, ldy, epilogue, config, workspace, workspace_bytes, stream);
+}
+
+// the weight exists as codes only: every tile id that has an 8-bit form (1 - 16 without 5), any M
+VDD_HIDDEN int VDD_IMPL(vdd_gemm_codes)(const void* X, const void* W8, const float* w_scale, void* Y, const void* bias, int M, int N, int K, int64_t ldx,
+             int64_t ldy, int epilogue, int config, void* workspace, int64_t workspace_bytes, void* stream) {
+    return gemm_on_codes(true, X, W8, w_scale, Y, bias, M, N, K, ldx, ldy, epilogue, config, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -81,6 +81,10 @@ VDD_MODEL_FN(vdd_gemm_w8,
              VDD_P(const void* X, const void* W8, const float* w_scale, void* Y, const void* bias, int M, int N, int K, int64_t ldx, int64_t ldy,
                    int epilogue, int config, void* workspace, int64_t workspace_bytes),
              VDD_P(X, W8, w_scale, Y, bias, M, N, K, ldx, ldy, epilogue, config, workspace, workspace_bytes))
+VDD_MODEL_FN(vdd_gemm_codes,
+             VDD_P(const void* X, const void* W8, const float* w_scale, void* Y, const void* bias, int M, int N, int K, int64_t ldx, int64_t ldy,
+                   int epilogue, int config, void* workspace, int64_t workspace_bytes),
+             VDD_P(X, W8, w_scale, Y, bias, M, N, K, ldx, ldy, epilogue, config, workspace, workspace_bytes))
 VDD_MODEL_FN(vdd_decode_attention,
              VDD_P(const void* q, const void* k_cache, const void* v_cache, const void* k_prefix, const void* v_prefix, const int32_t* rows, void* out,
                    void* workspace, int M, int H, int Hkv, int D, int64_t slot_stride, int t_max, int64_t prefix_stride, int prefix_tmax, int max_len,

@@ -221,6 +221,9 @@ def add_common_args(ap, help: Optional[dict] = None, dtype: str = "float16", **d
         ap.add_argument(flag, type=typ, help=(help or {}).get(dest), **(dict(required=True) if default is REQUIRED else dict(default=default)))
     ap.add_argument("--dtype", choices=("float16", "bfloat16"), default=dtype, help="model dtype (the reference loads LLaVA / Vicuna in fp16, builder.py:40)")
     ap.add_argument("--load-8bit", action="store_true", default=argparse.SUPPRESS, help="e4m3 weight storage for the few-row decode step (builder.py:26-31 load_8bit; VddLlavaEngine(load_8bit=True))")
+    ap.add_argument("--w8-only", action="store_true", default=argparse.SUPPRESS,
+                    help="with --load-8bit: keep the quantised language-model weights as e4m3 codes only - half the weight memory, every GEMM reads "
+                         "codes (VddLlavaEngine(load_8bit=True, w8_only=True))")
     ap.add_argument("--invariant-shared-prefix", action="store_true", default=argparse.SUPPRESS,
                     help="batch-invariant runs only: read an image prefix once per image (ops.INVARIANT_SHARED_PREFIX); still the same answers at any batch "
                          "size and rank count, but not the bits of a run without the option; open-ended lists (generate_list) refuse it")
@@ -229,8 +232,12 @@ def add_common_args(ap, help: Optional[dict] = None, dtype: str = "float16", **d
 
 
 def load_kw(a) -> dict:
-    """The loader / engine keywords the common options select: `load_8bit=True` after --load-8bit, nothing otherwise."""
-    return dict(load_8bit=True) if getattr(a, "load_8bit", False) else {}
+    """The loader / engine keywords the common options select: `load_8bit=True` after --load-8bit, `w8_only=True` after --w8-only (the
+    engine refuses it without --load-8bit), nothing otherwise."""
+    kw = dict(load_8bit=True) if getattr(a, "load_8bit", False) else {}
+    if getattr(a, "w8_only", False):
+        kw["w8_only"] = True
+    return kw
 
 
 def mode_kw(a) -> dict:

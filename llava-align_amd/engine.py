@@ -221,16 +221,38 @@ class LlavaWeights:
 
     W8_NAMES = ("wqkv", "wo", "wgu", "wd")
 
-    def quantize_lm_w8(self) -> "LlavaWeights":
+    def quantize_lm_w8(self, keep_w16: bool = True) -> "LlavaWeights":
         """load_8bit: every decoder layer's wqkv / wo / wgu / wd and lm_head (padded to a multiple of 8 rows, as LanguageModel pads it)
         become their e4m3 quantisation (ops.quantize_w8): t[name] <- w16, the dequantised 16-bit weight that every kernel of the package
         runs as before, and t[name + ".w8"] / t[name + ".w8s"] <- the codes and the power-of-two row scales that the few-row decode step
         streams instead.  Embeddings, norms, biases, vision tower and projector stay as they are.  Call it before the engine (its
-        LanguageModel) is built over these weights; a second call changes nothing."""
+        LanguageModel) is built over these weights; a second call changes nothing.
+        keep_w16=False (w8_only): t[name] becomes the ops.CodesWeight itself - codes + row scales and nothing else, lm_head padded to 8
+        rows inside the codes; the 16-bit tensor is released weight by weight as the loop goes, so the peak never holds both models.  A
+        weight whose K is not a multiple of 128 (no GEMM on codes) stays 16-bit, unquantised.  After a keep_w16=True call it drops the
+        w16 tensors and keeps the codes."""
         t, lm = self.t, self.cfg.lm
         names = [f"l{i}.{n}" for i in range(lm.n_layers) for n in self.W8_NAMES] + ["lm_head"]
+        if not keep_w16:
+            for name in names:
+                w = t[name]
+                if isinstance(w, ops.CodesWeight):
+                    continue
+                if name + ".w8" in t:                                   # quantised before, w16 kept until now
+                    t[name] = ops.CodesWeight(t.pop(name + ".w8"), t.pop(name + ".w8s"), w.dtype)
+                    continue
+                if w.shape[1] % 128 != 0:
+                    continue                                            # no kernel on codes for this depth: the weight stays 16-bit
+                if name == "lm_head" and w.shape[0] % 8 != 0:
+                    w = torch.nn.functional.pad(w, (0, 0, 0, (-w.shape[0]) % 8))
+                codes, scale, w16 = ops.quantize_w8(w)
+                m, _e = torch.frexp(scale)
+                assert bool((m == 0.5).all()), "8-bit row scales are powers of two"
+                del w, w16
+                t[name] = ops.CodesWeight(codes, scale, self.dtype)       # (the 16-bit tensor has no other owner inside these weights)
+            return self
         for name in names:
-            if name + ".w8" in t:
+            if name + ".w8" in t or isinstance(t[name], ops.CodesWeight):
                 continue
             w = t[name]
             if name == "lm_head" and w.shape[0] % 8 != 0:
@@ -245,15 +267,19 @@ class LlavaWeights:
 
     def w8(self, name: str):
         """(codes, scale) of weight `name` for the ops wrappers' `w8=`, or None for a weight that was not quantised."""
+        w = self.t.get(name)
+        if isinstance(w, ops.CodesWeight):
+            return w.codes, w.scale
         c = self.t.get(name + ".w8")
         return None if c is None else (c, self.t[name + ".w8s"])
 
     def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self.t.values())
+        return sum(t.nbytes() if isinstance(t, ops.CodesWeight) else t.numel() * t.element_size() for t in self.t.values())
 
     def lm_stream_bytes(self) -> int:
-        """Bytes a decode step must stream as 16-bit weights: every LM weight except the embedding table (gathered)."""
-        return sum(t.numel() * 2 for k, t in self.t.items()
+        """Bytes a decode step must stream as 16-bit weights: every LM weight except the embedding table (gathered).  A codes-only weight
+        (quantize_lm_w8(keep_w16=False)) counts one byte per code."""
+        return sum(t.numel() * (1 if isinstance(t, ops.CodesWeight) else 2) for k, t in self.t.items()
                    if ((k.startswith("l") and k[1].isdigit()) or k in ("norm", "lm_head")) and not k.endswith((".w8", ".w8s")))
 
 
@@ -521,7 +547,9 @@ class LanguageModel:
         # logits are a [rows, V] VIEW of its [rows, V_pad] result - the sampling kernel takes any row stride and never sees the padding.
         V = self.cfg.vocab
         self.lm_head = w.t["lm_head"]
-        if V % 8 != 0:
+        if isinstance(self.lm_head, ops.CodesWeight):
+            pass                                   # codes only: already padded to 8 rows inside the codes (quantize_lm_w8) - no 16-bit copy
+        elif V % 8 != 0:
             padded = torch.zeros((V + 7) // 8 * 8, self.lm_head.shape[1], dtype=self.lm_head.dtype, device=self.lm_head.device)
             padded[:V] = self.lm_head
             self.lm_head = padded
@@ -651,7 +679,8 @@ class LanguageModel:
             forms = lambda: dict(fused=lambda i: self._decode_step_few_rows(resid.clone(), pos, cpos, slot, attn_rows, kv),
                                  plain=lambda i: self._decode_layers(resid.clone(), pos, cpos, slot, attn_rows, kv, None, workspace),
                                  device=self.w.device, n_rot=1, iters=3)
-            if ops.norm_fused_pays(M, c.d, self.w.dtype, forms, w8=ops.W8_DECODE and self.w.w8("l0.wo") is not None):
+            codes_ks = (c.d, H * D, c.ffn) if isinstance(t["l0.wo"], ops.CodesWeight) else None
+            if ops.norm_fused_pays(M, c.d, self.w.dtype, forms, w8=ops.W8_DECODE and self.w.w8("l0.wo") is not None, codes_only_ks=codes_ks):
                 return self._decode_step_few_rows(resid, pos, cpos, slot, attn_rows, kv)
         return self._decode_layers(resid, pos, cpos, slot, attn_rows, kv, grouping, workspace)
 
@@ -1128,14 +1157,20 @@ class VddLlavaEngine:
 
     def __init__(self, cfg: LlavaConfig | str = "llava-1.5-7b", weights: Optional[LlavaWeights] = None, device="cuda:0",
                  seed: int = 0, max_questions: int = 64, t_max: int = 0, use_graph: bool = True, lm_head_gain: float = 1.0,
-                 dtype: Optional[torch.dtype] = None, load_8bit: bool = False, load_4bit: bool = False):
+                 dtype: Optional[torch.dtype] = None, load_8bit: bool = False, load_4bit: bool = False, w8_only: bool = False):
         """dtype: torch.bfloat16 (default; BASELINE config #2) or torch.float16 - the dtype every released driver of the reference loads
         its checkpoint in (builder.py:40, llava_calibrate.py:163).  With `weights` given, their dtype is the engine's.
         load_8bit (builder.py:26-31): the language model's projection weights and lm_head are quantised to e4m3 codes with power-of-two
         row scales (LlavaWeights.quantize_lm_w8, in place - `weights` included): the engine then runs the dequantised 16-bit model
         everywhere, and the few-row decode step streams the codes - half the bytes, the same bits.  This is weight-only e4m3 STORAGE,
         not bitsandbytes' LLM.int8 arithmetic; the 16-bit copy is kept for the prefill GEMM and every other path, so weight memory grows
-        by the codes (+6.6 GB at 7B)."""
+        by the codes (+6.6 GB at 7B).
+        w8_only (needs load_8bit): the quantised weights are kept as codes ONLY (LlavaWeights.quantize_lm_w8(keep_w16=False), in place) -
+        one byte per weight element instead of two (three with w16 kept).  Prefill, every decode row count, batch-invariant mode and
+        generate_list then run on the kernels that read codes (ops.CodesWeight; the MFMA GEMM through vdd_gemm_codes); nothing falls back
+        to a 16-bit weight, and ops.w8_decode(False) raises.  Vision tower, projector, embeddings, norms and biases stay 16-bit."""
+        if w8_only and not load_8bit:
+            raise ValueError("w8_only=True keeps the load_8bit codes as the only copy of the weights: pass load_8bit=True with it")
         if load_4bit:
             raise NotImplementedError("load_4bit: this package has no 4-bit weight form; load_8bit=True (e4m3 weight streaming) is the quantised option")
         self.cfg = preset(cfg) if isinstance(cfg, str) else cfg
@@ -1146,8 +1181,9 @@ class VddLlavaEngine:
         if self.dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"model dtype must be torch.bfloat16 or torch.float16 (got {self.dtype}): the kernels are built for those two")
         self.w = weights if weights is not None else LlavaWeights.random(self.cfg, self.device, seed, lm_head_gain=lm_head_gain, dtype=self.dtype)
+        self.w8_only = bool(w8_only)
         if load_8bit:
-            self.w.quantize_lm_w8()
+            self.w.quantize_lm_w8(keep_w16=not w8_only)
         self.vit = VisionTower(self.w)
         self.vit.use_graph = use_graph
         self.lm = LanguageModel(self.w)
@@ -1507,6 +1543,7 @@ class VddLlavaEngine:
         ctr0 = self._philox_counter(seed)
         eos_t = h2d_long(dev, eos_token_id) if eos_token_id is not None else None
         cfgkey = self._step_key(Q, nb, max_new_tokens, alpha, beta, warp, use_cd, use_dd, use_dd_unk, cd_greedy, eos_token_id, pad_token_id, output_scores)
+        cfgkey = cfgkey + (("w8_only", getattr(self, "w8_only", False)),)
         cpi = ops.INVARIANT_PREFIX_CHUNKS if inv_shared else ops.prefix_chunks_per_item(grp, lm.n_heads)
         n_groups, n_items = len(grp), len(inv_items) if inv_shared else len(ops.prefix_work_items(grp, cpi))
         cfgkey = cfgkey + (n_groups, n_items, cpi, inv_shared, proc_key)
@@ -1793,7 +1830,7 @@ class VddLlavaEngine:
         eos_t = h2d_long(dev, eos_token_id)
         ctr0 = self._philox_counter(seed)
         cfgkey = ("list", Qc, nb, max_new_tokens, alpha, beta, warp.t, warp.k, warp.p, use_dd, use_dd_unk, vcd, cd_greedy, tuple(eos_token_id), pad_token_id,
-                  ops.GEMM_BATCH_INVARIANT, ops.W8_DECODE) + (("paged",) if paged_kv else ())
+                  ops.GEMM_BATCH_INVARIANT, ops.W8_DECODE, ("w8_only", getattr(self, "w8_only", False))) + (("paged",) if paged_kv else ())
         if group_images:
             cfgkey = cfgkey + (("group_images", list_groups["cpi"], list_groups["items_capacity"], list_groups["invariant"]),)
         tail = dict(alpha=alpha, beta=beta, warp=warp, contrast=contrast, is_vcd=vcd, both=(use_dd and use_dd_unk), greedy=cd_greedy, eos_t=eos_t,
@@ -2206,7 +2243,7 @@ class VddLlavaEngine:
         embs = None if embs is None else tuple((e.data_ptr(), tuple(e.shape)) for e in embs)
         key = (tuple(map(tuple, ids_list)), ims, embs, tuple(embeds_prefix) if embeds_prefix is not None else None, branch_flags, share_prefix,
                self.two_level_prefix, self.share_repeated_rows, self.group_attention, ops.GEMM_BATCH_INVARIANT, str(self.dtype),
-               ops.invariant_shared_prefix())
+               ops.invariant_shared_prefix(), ("w8_only", getattr(self, "w8_only", False)))
         c = self._prefill_cache
         hit = c is not None and c["key"] == key and self._kvs.get(c["frag"]) is c["kv"] and max_new_tokens <= c["max_new"]
         return (c if hit else None), key

@@ -215,14 +215,17 @@ def _native_generate(model, inputs=None, generation_config=None, **kw):
     return res
 
 
-def attach_engine(model, share_storage: bool = True, use_graph: bool = True, max_questions: int = 64, load_8bit: bool = False) -> VddLlavaEngine:
+def attach_engine(model, share_storage: bool = True, use_graph: bool = True, max_questions: int = 64, load_8bit: bool = False,
+                  w8_only: bool = False) -> VddLlavaEngine:
     """Puts a `VddLlavaEngine` built from `model`'s own parameters behind `model.generate`.  Returns the engine (also at
     `model._vdd_engine`).  `detach_engine(model)` restores HF's generate (with the generic evolve_vcd_sampling() loop if installed).
     After a weight update (LoRA merge, resize_token_embeddings) attach again.  load_8bit: VddLlavaEngine(load_8bit=True) - the engine
-    decodes with its own e4m3-quantised copies of the language model's projections; `model`'s parameters stay as they are."""
+    decodes with its own e4m3-quantised copies of the language model's projections; `model`'s parameters stay as they are.  w8_only
+    (with load_8bit): the engine keeps codes only.  With share_storage=True the HF module keeps its own 16-bit parameters - the engine
+    drops only its references to them, so the memory is freed once `model` lets go of them too."""
     cfg = config_from_hf(model)
     w = weights_from_hf(model, cfg, share_storage=share_storage)
-    eng = VddLlavaEngine(cfg, weights=w, device=w.device, use_graph=use_graph, max_questions=max_questions, load_8bit=load_8bit)
+    eng = VddLlavaEngine(cfg, weights=w, device=w.device, use_graph=use_graph, max_questions=max_questions, load_8bit=load_8bit, w8_only=w8_only)
     model._vdd_engine = eng
     _set_guard(model)
     model.generate = types.MethodType(_native_generate, model)
@@ -349,13 +352,13 @@ def _native_lm_generate(lm, inputs=None, generation_config=None, **kw):
     return res
 
 
-def attach_lm_engine(lm, use_graph: bool = True, max_questions: int = 64, load_8bit: bool = False) -> VddLlavaEngine:
+def attach_lm_engine(lm, use_graph: bool = True, max_questions: int = 64, load_8bit: bool = False, w8_only: bool = False) -> VddLlavaEngine:
     """A language-model-only `VddLlavaEngine` behind `lm.generate` for a Llama-shaped or Qwen-shaped causal LM: what
     `Blip2VicunaInstruct.generate` calls as `self.llm_model.generate(inputs_embeds=..., images_cd=inputs_embeds_cd, ...)`
     (blip2_vicuna_instruct.py:390-410 - the reference's own EVA-ViT / Q-Former code then runs unchanged in front of the native LM)."""
     cfg = lm_config_from_hf(lm)
     eng = VddLlavaEngine(cfg, weights=lm_weights_from_hf(lm, cfg), device=lm.lm_head.weight.device, use_graph=use_graph, max_questions=max_questions,
-                         load_8bit=load_8bit)
+                         load_8bit=load_8bit, w8_only=w8_only)
     lm._vdd_engine = eng
     _set_guard(lm)
     lm.generate = types.MethodType(_native_lm_generate, lm)
@@ -430,7 +433,7 @@ def _native_blip_generate(model, samples, use_nucleus_sampling=False, num_beams=
     return text, out.scores[0]
 
 
-def attach_blip_engine(model, use_graph: bool = True, max_questions: int = 64, load_8bit: bool = False):
+def attach_blip_engine(model, use_graph: bool = True, max_questions: int = 64, load_8bit: bool = False, w8_only: bool = False):
     """The native front-end + engine behind a live `Blip2VicunaInstruct`-shaped object (`visual_encoder`, `ln_vision`, `Qformer`,
     `query_tokens`, `llm_proj`, `llm_model`, `tokenizer`, `llm_tokenizer`, `max_txt_len`): the driver's three calls per question
     (experiments/eval/calibrate/blip_calibrate.py:84-98) then run `model.generate({"image", "prompt"}, use_nucleus_sampling=True,
@@ -444,7 +447,7 @@ def attach_blip_engine(model, use_graph: bool = True, max_questions: int = 64, l
     if bcfg.d_llm != cfg.lm.d:
         raise ValueError(f"llm_proj maps to {bcfg.d_llm}, the language model is {cfg.lm.d} wide")
     front = InstructBlipFrontEnd(BlipWeights.from_state_dict(bcfg, sd, w.device, dtype=w.dtype))
-    eng = VddLlavaEngine(cfg, weights=w, device=w.device, use_graph=use_graph, max_questions=max_questions, load_8bit=load_8bit)
+    eng = VddLlavaEngine(cfg, weights=w, device=w.device, use_graph=use_graph, max_questions=max_questions, load_8bit=load_8bit, w8_only=w8_only)
     model._vdd_engine, model._vdd_front = eng, front
     model.generate = types.MethodType(_native_blip_generate, model)
     return eng, front
@@ -521,13 +524,14 @@ def _native_qwen_generate(model, inputs=None, generation_config=None, **kw):
     return out if return_dict else seqs
 
 
-def attach_qwen_engine(model, use_graph: bool = True, max_questions: int = 64, native_visual: bool = False, load_8bit: bool = False) -> VddLlavaEngine:
+def attach_qwen_engine(model, use_graph: bool = True, max_questions: int = 64, native_visual: bool = False, load_8bit: bool = False,
+                       w8_only: bool = False) -> VddLlavaEngine:
     """The native LM engine behind a `QWenLMHeadModel`-shaped object's `generate`; `model.transformer.visual` (the caller's ViT +
     resampler) keeps producing the 256 image rows per <img> span - or, with native_visual, the package's qwen_visual.QwenVisualTower
     built from that module's weights (`model._vdd_tower`) does."""
     cfg = lm_config_from_hf(model)
     eng = VddLlavaEngine(cfg, weights=lm_weights_from_hf(model, cfg), device=model.lm_head.weight.device, use_graph=use_graph,
-                         max_questions=max_questions, load_8bit=load_8bit)
+                         max_questions=max_questions, load_8bit=load_8bit, w8_only=w8_only)
     model._vdd_engine = eng
     if native_visual:
         from .qwen_visual import QwenVisualTower, QwenVisualWeights

@@ -46,6 +46,7 @@ _SIGS = {
     "vdd_skinny_gemm_normed_w8": [_P, _P, _I, _P, _F, _P, _P, _P, _I, _I, _I, _L, _L, _I, _P],
     "vdd_skinny_swiglu_normed_w8": [_P, _P, _I, _P, _F, _P, _P, _P, _I, _I, _I, _L, _I, _P],
     "vdd_gemm_w8": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _I, _I, _P, _L, _I, _P],
+    "vdd_gemm_codes": [_P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _I, _I, _P, _L, _I, _P],
     "vdd_skinny_gemm_w8": [_P, _P, _P, _P, _I, _I, _I, _L, _L, _I, _P],
     "vdd_skinny_swiglu_w8": [_P, _P, _P, _P, _I, _I, _I, _L, _I, _P],
     "vdd_rope_kv_write_paged": [_P] * 9 + [_I, _I, _I, _I, _L, _I, _I, _I, _I, _P],
@@ -191,6 +192,15 @@ def skinny_gemm(x, w, resid=None, out=None, n_split=1, slabs=False, w8=None):
     w8: (codes, scale) of w (quantize_w8) - the plain product streams them instead where vdd_skinny_gemm_w8 serves the call (K % 256 == 0;
     the same bits); with resid or slabs, w16 as ever."""
     N = w.shape[0]
+    if isinstance(w, CodesWeight):                 # codes only: the plain product, up to 64 rows, K % 256 == 0 (no residual / slab twin)
+        M, K = x.shape
+        q = _codes_call(w, x, "skinny_gemm")
+        if resid is not None or slabs or not _skinny_serves(M, K):
+            raise ValueError(f"skinny_gemm: no kernel on codes serves M={M} N={N} K={K} with a residual or slabs, or these rows")
+        out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+        _codes_launched(_lib_ready().vdd_skinny_gemm_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, N, K, x.stride(0),
+                                                        out.stride(0), _dt(x), _st(x)), "skinny_gemm", M, N, K)
+        return out
     q = _w8_args(w, w8)
     fn = _lib_ready().vdd_skinny_gemm
     dt = _dt(x, w, resid)
@@ -218,13 +228,19 @@ def gemm_slabs(x, w, n_split, out=None, tile=8, w8=None):
     """fp32 [n_split, M, N] partial products of x @ w^T (split-K over n_split parts of K, one (tile, part) per workgroup, no fix-up):
     for a consumer that adds them - rmsnorm(delta=slabs).  w8: (codes, scale) of w (quantize_w8) - streamed instead where vdd_gemm_w8
     serves the call (the same bits)."""
-    dt = _dt(x, w)
+    codes_only = isinstance(w, CodesWeight)
+    q = _codes_call(w, x, "gemm_slabs") if codes_only else None
+    dt = _dt(x) if codes_only else _dt(x, w)
     M, K = x.shape
     N = w.shape[0]
     if K % 128 != 0 or N % 4 != 0 or not 1 <= n_split <= min(255, K // 128):
         raise ValueError(f"gemm_slabs: K % 128, N % 4, 1 <= n_split <= K / 128 (got M={M} N={N} K={K} n_split={n_split})")
     out = torch.empty(n_split, M, N, dtype=torch.float32, device=x.device) if out is None else out
     ws = _gemm_workspace(x.device, M, N)
+    if codes_only:
+        _codes_launched(_lib_ready().vdd_gemm_codes(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), None, M, N, K, x.stride(0), N, EPI_NONE,
+                                                    tile + 16 * 3 + (n_split << 8), ws.data_ptr(), ws.numel(), dt, _st(x)), "gemm_slabs", M, N, K)
+        return out
     q = _w8_args(w, w8)
     if q is not None and _w8_done(_lib_ready().vdd_gemm_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), None, M, N, K,
                                                             x.stride(0), N, EPI_NONE, tile + 16 * 3 + (n_split << 8), ws.data_ptr(),
@@ -256,6 +272,18 @@ def linear_to_norm(x, w, w8=None):
     measurement, under a kind of its own."""
     M, K = x.shape
     N = w.shape[0]
+    if isinstance(w, CodesWeight):
+        _codes_call(w, x, "linear_to_norm")
+        cands = {}
+        s_ = slab_splits(M, N, K) if (M <= 256 and N <= 8192 and K % 256 == 0 and N % 4 == 0 and not GEMM_BATCH_INVARIANT) else 0
+        if K % 128 == 0 and N % 4 == 0:
+            cands["gemm8"] = lambda wi: gemm(x, wi)
+        if s_:
+            cands["slabs8"] = lambda wi: gemm_slabs(x, wi, s_)
+        if _codes_skinny_serves(M, K):
+            cands["skinny8"] = lambda wi: skinny_gemm(x, wi)
+        form = _pick_codes_form("to_norm" + CODES_KIND_SUFFIX, M, N, K, x, w, cands, consumer="norm")
+        return cands[form](w)
     cands = {}
     if _skinny_serves(M, K):
         cands["skinny"] = lambda wi: skinny_gemm(x, wi)
@@ -286,11 +314,11 @@ NORM_FUSED_MAX_M = 16   # rows up to which the normalise-once projections EXIST 
 
 FORCE_FORM = {}             # tests / probes: kind ("linear", "to_norm", "swiglu"; "linear8", "to_norm8", "swiglu8" with codes; those three + "i" in
                             # batch-invariant mode: "gemm" | "gemm8" only; "linear8t" of linear(keep_bits=True): "skinny" | "skinny8" only) -> "skinny" | "gemm" | "slabs" | "gemm8" | "slabs8" | "skinny8" wins
-                            # whenever it is eligible
+                            # whenever it is eligible; a CodesWeight (w8_only): "linearc", "to_normc", "swigluc" -> "gemm8" | "slabs8" | "skinny8"
 FORCE_LAYER_FORM = None     # tests / probes: "fused" | "plain" for every row count the fused layer serves
 
 
-def norm_fused_pays(M: int, d: int, dtype=torch.bfloat16, time_forms=None, w8: bool = False) -> bool:
+def norm_fused_pays(M: int, d: int, dtype=torch.bfloat16, time_forms=None, w8: bool = False, codes_only_ks=None) -> bool:
     """Does a decode step of M rows take the norm-fused five-launch layer (RMSNorms inside the projections around them) or the
     seven-launch layer (stand-alone norms, the projections in whatever form `_pick_form` measured)?  Measured once per (rows, d, dtype):
     `time_forms()` -> {"fused": fn(i), "plain": fn(i), "device", "n_rot", "iters"}: the engine passes the WHOLE decode step in either form
@@ -300,12 +328,16 @@ def norm_fused_pays(M: int, d: int, dtype=torch.bfloat16, time_forms=None, w8: b
     everywhere up to 16 rows except 9 - 12 (the normalise-once kernels change their block plan at 9 rows); d = 5120 only up to 7 rows
     (above, its d-wide projections are faster as split-K slabs, which need the stand-alone norms).  Never in batch-invariant mode.
     w8: the fused layer streams 8-bit weight codes (quantize_w8) - another kernel set, measured under a key of its own (8 in the fourth
-    slot) and never read from the 16-bit choices."""
+    slot) and never read from the 16-bit choices.
+    codes_only_ks: the layer's weights are CodesWeights with these contraction depths (d, heads x head_dim, ffn) - the fused entries on codes
+    take K % 256 == 0 and there is no 16-bit twin to run instead, so any other depth answers "plain" (key: 16 in the fourth slot)."""
     if GEMM_BATCH_INVARIANT or M > norm_fused_rows(d):
+        return False
+    if codes_only_ks is not None and (not W8_DECODE or any(k % 256 != 0 for k in codes_only_ks)):
         return False
     if FORCE_LAYER_FORM is not None:
         return FORCE_LAYER_FORM == "fused"
-    key = ("layer", M, d, 8 if w8 else 0, _MODEL_DT[dtype])
+    key = ("layer", M, d, 16 if codes_only_ks is not None else (8 if w8 else 0), _MODEL_DT[dtype])
     got = _form_choice.get(key)
     if got is None and time_forms is not None and GEMM_AUTOTUNE and not torch.cuda.is_current_stream_capturing():
         tf = time_forms()                                  # built only when a measurement is really due
@@ -463,14 +495,119 @@ def _w8_done(rc) -> bool:
     return True
 
 
+# ---- codes-only weights (load_8bit with w8_only): the quantised weight exists ONLY as e4m3 codes + row scales - no w16 beside them, so weight
+# memory is 1 byte per element + 4 per row.  A CodesWeight goes wherever a projection weight goes; every wrapper then has exactly the forms
+# that read codes - the GEMM on codes (vdd_gemm_codes: any M, the universal form), its slabs, the weight-streaming kernels on codes and the
+# few-row fused entries - measured under kinds and GEMM keys of their own, and raises where none serves the call: nothing falls back to 16 bits.
+W8_CODES_TILES = (1, 2, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16)      # vdd_gemm_codes: every tile id but 5 (256 x 192: 12 code images, 8 waves)
+CODES_KIND_SUFFIX = "c"     # form kinds of a CodesWeight: "linearc", "to_normc", "swigluc" ("gemm8" | "slabs8" | "skinny8")
+
+
+class CodesWeight:
+    """A [N, K] projection weight held as codes only: `codes` uint8 [N, K] in the kernels' storage order and `scale` fp32 [N] powers of two
+    (quantize_w8), standing for the `dtype` (bf16 / fp16) weight code * scale."""
+    __slots__ = ("codes", "scale", "dtype")
+
+    def __init__(self, codes: torch.Tensor, scale: torch.Tensor, dtype):
+        if codes.dtype != torch.uint8 or codes.dim() != 2 or scale.dtype != torch.float32 or scale.dim() != 1 or scale.shape[0] != codes.shape[0] \
+                or not codes.is_contiguous() or not scale.is_contiguous() or codes.device != scale.device or codes.shape[1] % W8_GROUP != 0:
+            raise ValueError("CodesWeight(uint8 codes [N, K] from quantize_w8, fp32 scale [N], dtype)")
+        if dtype not in _MODEL_DT:
+            raise ValueError("CodesWeight stands for a bf16 or fp16 weight")
+        self.codes, self.scale, self.dtype = codes, scale, dtype
+
+    shape = property(lambda self: self.codes.shape)
+    device = property(lambda self: self.codes.device)
+
+    def dim(self) -> int:
+        return 2
+
+    def numel(self) -> int:
+        return self.codes.numel()
+
+    def nbytes(self) -> int:
+        """Device bytes: one per code, four per row."""
+        return self.codes.numel() + 4 * self.scale.numel()
+
+    def clone(self) -> "CodesWeight":
+        """Another copy of the codes (the tuners rotate through copies so that none is cache-resident); the scales are shared."""
+        return CodesWeight(self.codes.clone(), self.scale, self.dtype)
+
+    def dequantize(self) -> torch.Tensor:
+        """The 16-bit weight the codes stand for (tests, references) - exact."""
+        return w8_dequantize(self.codes, self.scale, self.dtype)
+
+
+def _codes_call(w: CodesWeight, x, what: str):
+    """The checks every call on a CodesWeight makes: the switch (there is no w16 to stream instead) and the operands."""
+    if not W8_DECODE:
+        raise RuntimeError(f"{what}: ops.w8_decode(False) with a codes-only weight - there is no 16-bit weight to stream instead")
+    if x.dtype != w.dtype or x.device != w.device:
+        raise ValueError(f"{what}: activations {x.dtype} on {x.device}, codes-only weight for {w.dtype} on {w.device}")
+    return w.codes, w.scale
+
+
+def _codes_launched(rc, what, M, N, K):
+    """Status of an 8-bit entry on a codes-only weight: launched (counted) - a shape it does not serve is an error here."""
+    if rc == _VDD_ERR_UNSUPPORTED:
+        raise ValueError(f"{what}: no kernel on codes serves M={M} N={N} K={K}")
+    _lib.check(rc)
+    _w8_launches[0] += 1
+
+
+def _pick_codes_form(kind, M, N, K, x, w: CodesWeight, cands, consumer=None):
+    """_pick_form for a CodesWeight: `cands` (name -> fn(CodesWeight)) hold forms on codes only.  Batch-invariant mode: the GEMM on codes
+    (its data-parallel schedule).  Else the measured one, under `kind` (a kind of its own) and timed on rotating copies of the codes."""
+    if not cands:
+        raise ValueError(f"{kind}: no kernel on codes serves M={M} N={N} K={K} (the GEMM on codes takes K % 128 == 0 and N % 4 == 0)")
+    if GEMM_BATCH_INVARIANT and "gemm8" in cands:
+        return "gemm8"
+    if len(cands) == 1:
+        return next(iter(cands))
+    if FORCE_FORM.get(kind) in cands:
+        return FORCE_FORM[kind]
+    key = _form_key(kind, M, N, K, _MODEL_DT[x.dtype])
+    got = _form_choice.get(key)
+    if got is not None and got in cands:
+        return got
+    fallback = "skinny8" if ("skinny8" in cands and M <= FALLBACK_SKINNY_ROWS) else ("gemm8" if "gemm8" in cands else next(iter(cands)))
+    if not GEMM_AUTOTUNE or torch.cuda.is_current_stream_capturing():
+        return fallback
+    n_copies = int(min(24, max(2, -(-640 * 2 ** 20 // w.numel()))))
+    try:
+        copies = [w] + [w.clone() for _ in range(n_copies - 1)]
+    except torch.OutOfMemoryError:
+        copies = [w]
+    run = {n_: (lambda i, f=f: f(copies[i])) for n_, f in cands.items()}
+    if consumer == "norm":
+        res, lnw = torch.zeros(M, N, dtype=x.dtype, device=x.device), torch.ones(N, dtype=x.dtype, device=x.device)
+        thunks = {n_: (lambda i, f=f: rmsnorm(res, lnw, 1e-5, delta=f(i))) for n_, f in run.items()}
+    else:
+        thunks = run
+    got = _pick_timed(key, thunks, x.device, len(copies))
+    return got if got is not None else fallback
+
+
+def _codes_skinny_serves(M, K) -> bool:
+    """The weight-streaming kernels on codes: up to 64 rows, K % 256 == 0; never in batch-invariant mode (they split K over waves)."""
+    return not GEMM_BATCH_INVARIANT and M <= 64 and K % 256 == 0
+
+
 def linear_resid_ss(x, w, resid, out=None, ss=None, w8=None):
     """h = bf16(bf16(x w^T) + resid) (the new residual stream) and ss [M, N/16] fp32: per-block partial sums of squares of h's rows,
     for linear_normed / swiglu_linear_normed.  M <= NORM_FUSED_MAX_M.  w8: (codes, scale) of w (quantize_w8) - streamed instead."""
-    dt = _dt(x, w, resid)
+    codes_only = isinstance(w, CodesWeight)
+    q = _codes_call(w, x, "linear_resid_ss") if codes_only else None
+    dt = _dt(x, resid) if codes_only else _dt(x, w, resid)
     M, K = x.shape
     N = w.shape[0]
     out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
     ss = torch.empty(M, (N + 15) // 16, dtype=torch.float32, device=x.device) if ss is None else ss
+    if codes_only:
+        _codes_launched(_lib_ready().vdd_skinny_gemm_resid_ss_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), resid.data_ptr(), out.data_ptr(),
+                                                                 ss.data_ptr(), M, N, K, x.stride(0), resid.stride(0), out.stride(0), dt, _st(x)),
+                        "linear_resid_ss", M, N, K)
+        return out, ss
     q = _w8_args(w, w8)
     if q is not None and _w8_done(_lib_ready().vdd_skinny_gemm_resid_ss_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), resid.data_ptr(),
                                                                             out.data_ptr(), ss.data_ptr(), M, N, K, x.stride(0),
@@ -483,10 +620,17 @@ def linear_resid_ss(x, w, resid, out=None, ss=None, w8=None):
 
 def linear_normed(h, ss, ln_w, eps, w, out=None, bias=None, w8=None):
     """rmsnorm(h; ln_w, eps) @ w^T with the normalisation done as h's fragments load (h, ss from linear_resid_ss)."""
-    dt = _dt(h, w, ln_w)
+    codes_only = isinstance(w, CodesWeight)
+    q = _codes_call(w, h, "linear_normed") if codes_only else None
+    dt = _dt(h, ln_w) if codes_only else _dt(h, w, ln_w)
     M, K = h.shape
     N = w.shape[0]
     out = torch.empty(M, N, dtype=h.dtype, device=h.device) if out is None else out
+    if codes_only:
+        _codes_launched(_lib_ready().vdd_skinny_gemm_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, q[0].data_ptr(),
+                                                               q[1].data_ptr(), out.data_ptr(), M, N, K, h.stride(0), out.stride(0), dt, _st(h)),
+                        "linear_normed", M, N, K)
+        return bias_act(out, bias, out=out) if bias is not None else out
     q = _w8_args(w, w8)
     if not (q is not None and _w8_done(_lib_ready().vdd_skinny_gemm_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps,
                                                                                q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, N, K,
@@ -497,10 +641,17 @@ def linear_normed(h, ss, ln_w, eps, w, out=None, bias=None, w8=None):
 
 
 def swiglu_linear_normed(h, ss, ln_w, eps, w_gate_up, out=None, w8=None):
-    dt = _dt(h, w_gate_up, ln_w)
+    codes_only = isinstance(w_gate_up, CodesWeight)
+    q = _codes_call(w_gate_up, h, "swiglu_linear_normed") if codes_only else None
+    dt = _dt(h, ln_w) if codes_only else _dt(h, w_gate_up, ln_w)
     M, K = h.shape
     F = w_gate_up.shape[0] // 2
     out = torch.empty(M, F, dtype=h.dtype, device=h.device) if out is None else out
+    if codes_only:
+        _codes_launched(_lib_ready().vdd_skinny_swiglu_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, q[0].data_ptr(),
+                                                                 q[1].data_ptr(), out.data_ptr(), M, F, K, h.stride(0), dt, _st(h)),
+                        "swiglu_linear_normed", M, 2 * F, K)
+        return out
     q = _w8_args(w_gate_up, w8)
     if q is not None and _w8_done(_lib_ready().vdd_skinny_swiglu_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps,
                                                                             q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, F, K,
@@ -729,9 +880,11 @@ def gemm_workspace_reset(device=None):
             ws[: 4 << 20].zero_()
 
 
-def _gemm_w8_call(x, q, out, bias, M, N, K, epi, config, ws) -> bool:
-    """vdd_gemm_w8 on q = (codes, scale): True = launched (and counted), False = not served (nothing launched, `out` untouched)."""
-    return _w8_done(_lib_ready().vdd_gemm_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else None,
+def _gemm_w8_call(x, q, out, bias, M, N, K, epi, config, ws, codes_only=False) -> bool:
+    """vdd_gemm_w8 (codes_only: vdd_gemm_codes) on q = (codes, scale): True = launched (and counted), False = not served (nothing launched,
+    `out` untouched)."""
+    lib = _lib_ready()
+    return _w8_done((lib.vdd_gemm_codes if codes_only else lib.vdd_gemm_w8)(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else None,
                                              M, N, K, x.stride(0), out.stride(0), epi, config, ws.data_ptr(), ws.numel(), _MODEL_DT[x.dtype], _st(x)))
 
 
@@ -748,6 +901,8 @@ def gemm(x, w, bias=None, resid=None, epi=EPI_NONE, out=None, config=None, w8=No
     w8: (codes, scale) of w (quantize_w8).  With ops.W8_DECODE on and a `config` vdd_gemm_w8 serves, the codes are streamed instead of w -
     the same bits (include/vdd_hip.h); config=None: tile and schedule tuned among the W-stream tiles under a key of its own; anything the
     8-bit entry does not serve runs as ever on w."""
+    if isinstance(w, CodesWeight):
+        return _gemm_codes(x, w, bias, resid, epi, out, config)
     q = _w8_args(w, w8)
     dt = _dt(x, w, bias, resid)
     M, K = x.shape
@@ -783,6 +938,54 @@ def gemm(x, w, bias=None, resid=None, epi=EPI_NONE, out=None, config=None, w8=No
                 _gemm_choice[key] = config
     _gemm_call(x, w, out, bias, resid, M, N, K, epi, config, ws)
     return out
+
+
+def _gemm_codes(x, w: CodesWeight, bias, resid, epi, out, config):
+    """gemm() on a CodesWeight: vdd_gemm_codes - any M, epilogues NONE / BIAS / SWIGLU.  config=None: tile and schedule tuned among
+    W8_CODES_TILES under a key family of its own (`_gemm_key_codes`); where that cannot be measured (a capture in progress, the tuner off,
+    M above GEMM_TUNE_MAX_M) the 256 x 256 tile, hybrid schedule (batch-invariant mode: data-parallel).  Nothing falls back to 16 bits."""
+    q = _codes_call(w, x, "gemm")
+    dt = _dt(x, bias)
+    M, K = x.shape
+    N = w.shape[0] // 2 if epi == EPI_SWIGLU else w.shape[0]
+    if K != w.shape[1] or K % 128 != 0 or N % 4 != 0 or x.stride(1) != 1 or resid is not None or epi not in (EPI_NONE, EPI_BIAS, EPI_SWIGLU) \
+            or (epi == EPI_SWIGLU and N % 128 != 0):
+        raise ValueError(f"gemm on codes needs K % 128 == 0, N % 4 == 0 (SwiGLU: F % 128 == 0), no residual and the epilogues NONE / BIAS / SWIGLU "
+                         f"(got M={M} N={N} K={K} epi={epi})")
+    out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+    if M == 0:
+        return out
+    ws = _gemm_workspace(x.device, M, N)
+    if config is None:
+        key = _gemm_key_codes(M, N, K, epi, dt)
+        config = _gemm_choice.get(key)
+        if config is None and GEMM_AUTOTUNE:
+            _load_persisted(x.device)
+            config = _gemm_choice.get(key)
+        if config is None:
+            config = gemm_config(1, 1) if GEMM_BATCH_INVARIANT else gemm_config(1, 0)
+            if M <= GEMM_TUNE_MAX_M and GEMM_AUTOTUNE:
+                if not torch.cuda.is_current_stream_capturing():
+                    with _CacheLock():
+                        _read_cache_section()
+                        got = _gemm_choice.get(key)
+                        if got is None:
+                            got = _gemm_tune(x, None, out, bias, None, M, N, K, epi, ws, w8=q, codes_only=True)
+                            if got is not None:
+                                _gemm_choice[key] = got
+                                _store_persisted(key, got)
+                        config = got if got is not None else config
+            else:
+                _gemm_choice[key] = config
+    if not _gemm_w8_call(x, q, out, bias, M, N, K, epi, config, ws, codes_only=True):
+        raise ValueError(f"gemm on codes: config {config} (tile id {(config & 15) | ((config >> 6) << 4)}) is not served for M={M} N={N} K={K} epi={epi}")
+    return out
+
+
+def _gemm_key_codes(M, N, K, epi, dt):
+    """Tuning key of the GEMM on a codes-only weight: 16 added to the storage type (17 fp16, 18 bf16) - a family beside the 16-bit keys and
+    those of load_8bit with w16 kept (`_gemm_key_w8`), so neither is read or overwritten."""
+    return _gemm_key(M, N, K, epi, dt + 16)
 
 
 def _gemm_key_w8(M, N, K, epi, dt):
@@ -1009,13 +1212,13 @@ def _store_persisted(key, cfg):
         pass
 
 
-def _gemm_tune(x, w, out, bias, resid, M, N, K, epi, ws, iters=8, w8=None):
+def _gemm_tune(x, w, out, bias, resid, M, N, K, epi, ws, iters=8, w8=None, codes_only=False):
     """Times every (tile shape, schedule) candidate on the real operands and keeps the fastest (all write the same result).
     In the decode step a projection's weights always come from HBM (13 GB of them stream through per step), so the timed launches
     rotate through enough copies of `w` that none is still in the 256-MiB Infinity Cache when its turn comes again: timed on ONE
     hot copy the tuner preferred small macro tiles that then ran 10 % slower in place.
     w8 = (codes, scale): the GEMM on codes instead (w unused) - the candidates are those of W8_GEMM_TILES, the copies are copies of the
-    codes, and the result is None if the 8-bit entry serves none of them."""
+    codes, and the result is None if the 8-bit entry serves none of them.  codes_only: vdd_gemm_codes and W8_CODES_TILES instead."""
     src = w if w8 is None else w8[0]
     n_copies = int(min(24, max(2, -(-640 * 2 ** 20 // (src.numel() * src.element_size())))))
     try:
@@ -1029,8 +1232,8 @@ def _gemm_tune(x, w, out, bias, resid, M, N, K, epi, ws, iters=8, w8=None):
         candidates, best = GEMM_CANDIDATES, 1
     else:
         def call(ci, cfg):
-            return _gemm_w8_call(x, (ci, w8[1]), out, bias, M, N, K, epi, cfg, ws)
-        candidates, best = [(c, s_) for (c, s_) in GEMM_CANDIDATES if c in W8_GEMM_TILES], None
+            return _gemm_w8_call(x, (ci, w8[1]), out, bias, M, N, K, epi, cfg, ws, codes_only=codes_only)
+        candidates, best = [(c, s_) for (c, s_) in GEMM_CANDIDATES if c in (W8_CODES_TILES if codes_only else W8_GEMM_TILES)], None
     best_t = float("inf")
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     turn = 0
@@ -1076,6 +1279,18 @@ def linear(x, w, out=None, bias=None, w8=None, keep_bits=False):
     measured faster (kind "linear8t": a pair with the same bits) - for a caller that promises the bits of its 16-bit run (the few-row step)."""
     M, K = x.shape
     N = w.shape[0]
+    if isinstance(w, CodesWeight):                 # (keep_bits: the forms on codes are all there is)
+        _codes_call(w, x, "linear")
+        cands = {}
+        if K % 128 == 0 and N % 4 == 0:
+            cands["gemm8"] = lambda wi: gemm(x, wi)
+        if _codes_skinny_serves(M, K):
+            cands["skinny8"] = lambda wi: skinny_gemm(x, wi)
+        form = _pick_codes_form("linear" + CODES_KIND_SUFFIX, M, N, K, x, w, cands)
+        if form == "skinny8":
+            y = skinny_gemm(x, w, out=out)
+            return bias_act(y, bias, out=y) if bias is not None else y
+        return gemm(x, w, bias=bias, epi=EPI_BIAS if bias is not None else EPI_NONE, out=out)
     cands = {}
     if _skinny_serves(M, K):
         cands["skinny"] = lambda wi: skinny_gemm(x, wi)
@@ -1105,6 +1320,12 @@ def linear(x, w, out=None, bias=None, w8=None, keep_bits=False):
 def _skinny_swiglu(x, w_gate_up, out=None, w8=None):
     M, K = x.shape
     F = w_gate_up.shape[0] // 2
+    if isinstance(w_gate_up, CodesWeight):
+        q = _codes_call(w_gate_up, x, "swiglu_linear")
+        out = torch.empty(M, F, dtype=x.dtype, device=x.device) if out is None else out
+        _codes_launched(_lib_ready().vdd_skinny_swiglu_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, F, K, x.stride(0),
+                                                          _dt(x), _st(x)), "swiglu_linear", M, 2 * F, K)
+        return out
     q = _w8_args(w_gate_up, w8)
     dt = _dt(x, w_gate_up)
     out = torch.empty(M, F, dtype=x.dtype, device=x.device) if out is None else out
@@ -1120,6 +1341,17 @@ def swiglu_linear(x, w_gate_up, out=None, w8=None):
     block; 17 - 64: 16, gate + up tiles) or the MFMA GEMM with the SwiGLU epilogue (no [M, 2F] round trip, no silu_mul launch); measured."""
     M, K = x.shape
     F = w_gate_up.shape[0] // 2
+    if isinstance(w_gate_up, CodesWeight):
+        _codes_call(w_gate_up, x, "swiglu_linear")
+        cands = {}
+        if K % 128 == 0 and F % 128 == 0:
+            cands["gemm8"] = lambda wi, o=None: gemm(x, wi, epi=EPI_SWIGLU, out=o)
+        elif K % 128 == 0 and F % 8 == 0:                   # (odd feature counts: the plain GEMM on codes + vdd_silu_mul)
+            cands["gemm8"] = lambda wi, o=None: silu_mul(gemm(x, wi), out=o)
+        if _codes_skinny_serves(M, K):
+            cands["skinny8"] = lambda wi, o=None: _skinny_swiglu(x, wi, o)
+        form = _pick_codes_form("swiglu" + CODES_KIND_SUFFIX, M, 2 * F, K, x, w_gate_up, {k: (lambda wi, f=f: f(wi)) for k, f in cands.items()})
+        return cands[form](w_gate_up, out)
     cands = {}
     if K % 128 == 0 and F % 128 == 0:
         cands["gemm"] = lambda wi, o=None: gemm(x, wi, epi=EPI_SWIGLU, out=o)
