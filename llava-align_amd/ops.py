@@ -190,32 +190,26 @@ def skinny_gemm(x, w, resid=None, out=None, n_split=1, slabs=False, w8=None):
     """x [M<=64, K] @ w[N, K]^T (+ resid [M, N]) -> [M, N]; streams w from HBM exactly once.
     slabs=True: returns the fp32 split-K partials [n_split, M, N] instead (feed them to rmsnorm as `delta`).
     w8: (codes, scale) of w (quantize_w8) - the plain product streams them instead where vdd_skinny_gemm_w8 serves the call (K % 256 == 0;
-    the same bits); with resid or slabs, w16 as ever."""
-    N = w.shape[0]
-    if isinstance(w, CodesWeight):                 # codes only: the plain product, up to 64 rows, K % 256 == 0 (no residual / slab twin)
-        M, K = x.shape
-        q = _codes_call(w, x, "skinny_gemm")
-        if resid is not None or slabs or not _skinny_serves(M, K):
-            raise ValueError(f"skinny_gemm: no kernel on codes serves M={M} N={N} K={K} with a residual or slabs, or these rows")
-        out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
-        _codes_launched(_lib_ready().vdd_skinny_gemm_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, N, K, x.stride(0),
-                                                        out.stride(0), _dt(x), _st(x)), "skinny_gemm", M, N, K)
-        return out
-    q = _w8_args(w, w8)
-    fn = _lib_ready().vdd_skinny_gemm
-    dt = _dt(x, w, resid)
+    the same bits); with resid or slabs, w16 as ever (a CodesWeight has no residual / slab twin: that raises)."""
+    src = _weight_source(w, w8, x, "skinny_gemm")
     M, K = x.shape
+    N = src.shape[0]
+    if src.strict and (resid is not None or slabs or not _skinny_serves(M, K)):
+        raise ValueError(f"skinny_gemm: no kernel on codes serves M={M} N={N} K={K} with a residual or slabs, or these rows")
+    dt = _dt(x, src.w16, resid)
     if slabs:
         out = torch.empty(n_split, M, N, dtype=torch.float32, device=x.device) if out is None else out
-        _lib.check(fn(x.data_ptr(), w.data_ptr(), None, None, out.data_ptr(), n_split, M, N, K, x.stride(0), 0, N, dt, _st(x)))
-        return out
-    out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
-    if q is not None and resid is None and _w8_done(_lib_ready().vdd_skinny_gemm_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, N, K,
-                                                                                     x.stride(0), out.stride(0), dt, _st(x))):
-        return out
-    _lib.check(fn(x.data_ptr(), w.data_ptr(), resid.data_ptr() if resid is not None else None,
-                  out.data_ptr(), None, 1, M, N, K, x.stride(0), resid.stride(0) if resid is not None else 0,
-                  out.stride(0), dt, _st(x)))
+        resid = None
+    else:
+        out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
+
+    def on16():
+        _lib.check(_lib_ready().vdd_skinny_gemm(x.data_ptr(), src.w16.data_ptr(), resid.data_ptr() if resid is not None else None,
+                                                None if slabs else out.data_ptr(), out.data_ptr() if slabs else None, n_split if slabs else 1,
+                                                M, N, K, x.stride(0), resid.stride(0) if resid is not None else 0,
+                                                N if slabs else out.stride(0), dt, _st(x)))
+    _launch(src if resid is None and not slabs else src.plain(), "skinny_gemm", M, N, K,
+            lambda cp, sp: _lib_ready().vdd_skinny_gemm_w8(x.data_ptr(), cp, sp, out.data_ptr(), M, N, K, x.stride(0), out.stride(0), dt, _st(x)), on16)
     return out
 
 
@@ -228,26 +222,17 @@ def gemm_slabs(x, w, n_split, out=None, tile=8, w8=None):
     """fp32 [n_split, M, N] partial products of x @ w^T (split-K over n_split parts of K, one (tile, part) per workgroup, no fix-up):
     for a consumer that adds them - rmsnorm(delta=slabs).  w8: (codes, scale) of w (quantize_w8) - streamed instead where vdd_gemm_w8
     serves the call (the same bits)."""
-    codes_only = isinstance(w, CodesWeight)
-    q = _codes_call(w, x, "gemm_slabs") if codes_only else None
-    dt = _dt(x) if codes_only else _dt(x, w)
+    src = _weight_source(w, w8, x, "gemm_slabs")
+    _dt(x, src.w16)
     M, K = x.shape
-    N = w.shape[0]
+    N = src.shape[0]
     if K % 128 != 0 or N % 4 != 0 or not 1 <= n_split <= min(255, K // 128):
         raise ValueError(f"gemm_slabs: K % 128, N % 4, 1 <= n_split <= K / 128 (got M={M} N={N} K={K} n_split={n_split})")
     out = torch.empty(n_split, M, N, dtype=torch.float32, device=x.device) if out is None else out
     ws = _gemm_workspace(x.device, M, N)
-    if codes_only:
-        _codes_launched(_lib_ready().vdd_gemm_codes(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), None, M, N, K, x.stride(0), N, EPI_NONE,
-                                                    tile + 16 * 3 + (n_split << 8), ws.data_ptr(), ws.numel(), dt, _st(x)), "gemm_slabs", M, N, K)
-        return out
-    q = _w8_args(w, w8)
-    if q is not None and _w8_done(_lib_ready().vdd_gemm_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), None, M, N, K,
-                                                            x.stride(0), N, EPI_NONE, tile + 16 * 3 + (n_split << 8), ws.data_ptr(),
-                                                            ws.numel(), dt, _st(x))):
-        return out
-    _lib.check(_lib_ready().vdd_gemm(x.data_ptr(), w.data_ptr(), out.data_ptr(), None, None, M, N, K, x.stride(0), w.stride(0), N, 0,
-                                     EPI_NONE, tile + 16 * 3 + (n_split << 8), ws.data_ptr(), ws.numel(), dt, _st(x)))
+    config, slab0 = tile + 16 * 3 + (n_split << 8), out[0]         # (slab 0: the [M, N] image whose row stride the entries take, N)
+    _launch(src, "gemm_slabs", M, N, K, lambda cp, sp: _gemm8_rc(src.strict, x, cp, sp, slab0, None, M, N, K, EPI_NONE, config, ws),
+            lambda: _gemm_call(x, src.w16, slab0, None, None, M, N, K, EPI_NONE, config, ws))
     return out
 
 
@@ -269,52 +254,25 @@ def linear_to_norm(x, w, w8=None):
     re-reads X per column block and, when N / 16 column blocks do not divide over the CUs (d = 5120: 320 blocks on 256), runs a second
     round for a quarter of the chip.
     w8: (codes, scale) of w - the GEMM, the slabs and the weight-streaming kernel on codes ("gemm8", "slabs8", "skinny8") join the
-    measurement, under a kind of its own."""
+    measurement, under a kind of its own; a CodesWeight has those three alone."""
+    src = _weight_source(w, w8, x, "linear_to_norm")
     M, K = x.shape
-    N = w.shape[0]
-    if isinstance(w, CodesWeight):
-        _codes_call(w, x, "linear_to_norm")
-        cands = {}
-        s_ = slab_splits(M, N, K) if (M <= 256 and N <= 8192 and K % 256 == 0 and N % 4 == 0 and not GEMM_BATCH_INVARIANT) else 0
-        if K % 128 == 0 and N % 4 == 0:
-            cands["gemm8"] = lambda wi: gemm(x, wi)
-        if s_:
-            cands["slabs8"] = lambda wi: gemm_slabs(x, wi, s_)
-        if _codes_skinny_serves(M, K):
-            cands["skinny8"] = lambda wi: skinny_gemm(x, wi)
-        form = _pick_codes_form("to_norm" + CODES_KIND_SUFFIX, M, N, K, x, w, cands, consumer="norm")
-        return cands[form](w)
-    cands = {}
-    if _skinny_serves(M, K):
-        cands["skinny"] = lambda wi: skinny_gemm(x, wi)
-    if K % 128 == 0 and N % 4 == 0:
-        cands["gemm"] = lambda wi: gemm(x, wi)
+    N = src.shape[0]
     s_ = slab_splits(M, N, K) if (M <= 256 and N <= 8192 and K % 256 == 0) else 0
-    if s_:
-        cands["slabs"] = lambda wi: gemm_slabs(x, wi, s_)
-    q = _w8_form_args(w, w8, M, K, N)
-    if q is not None:
-        cands["gemm8"] = lambda wi, qi: gemm(x, wi, w8=qi)
-        if s_:
-            cands["slabs8"] = lambda wi, qi: gemm_slabs(x, wi, s_, w8=qi)
-    qs = _w8_skinny_args(w, w8, M, K) if "skinny" in cands else None
-    if qs is not None:
-        cands["skinny8"] = lambda wi, qi: skinny_gemm(x, wi, w8=qi)
-    q8 = q if q is not None else qs
-    form = _pick_form("to_norm8" if q8 is not None else "to_norm", M, N, K, x, w, cands, consumer="norm", w8=q8)
-    if form in ("slabs", "slabs8"):
-        return gemm_slabs(x, w, s_, w8=q if form == "slabs8" else None)
-    if form in ("skinny", "skinny8"):
-        return skinny_gemm(x, w, w8=qs if form == "skinny8" else None)
-    return gemm(x, w, w8=q if form == "gemm8" else None)
+    src, cands = _form_cands(src, {
+        "skinny": (_skinny_serves(M, K), src.skinny8_ok(M, K), lambda s: skinny_gemm(x, s)),
+        "gemm": (K % 128 == 0 and N % 4 == 0, src.gemm8_ok(M, N, K), lambda s: gemm(x, s)),
+        "slabs": (s_ > 0, s_ > 0 and src.gemm8_ok(M, N, K) and not (src.strict and GEMM_BATCH_INVARIANT), lambda s: gemm_slabs(x, s, s_))})
+    return cands[_pick_form("to_norm" + src.kind_suffix, M, N, K, x, src, cands, consumer="norm")](src)
 
 
 NORM_FUSED_MAX_M = 16   # rows up to which the normalise-once projections EXIST (their LDS image of the normalised rows; see norm_fused_rows)
 
 
-FORCE_FORM = {}             # tests / probes: kind ("linear", "to_norm", "swiglu"; "linear8", "to_norm8", "swiglu8" with codes; those three + "i" in
-                            # batch-invariant mode: "gemm" | "gemm8" only; "linear8t" of linear(keep_bits=True): "skinny" | "skinny8" only) -> "skinny" | "gemm" | "slabs" | "gemm8" | "slabs8" | "skinny8" wins
-                            # whenever it is eligible; a CodesWeight (w8_only): "linearc", "to_normc", "swigluc" -> "gemm8" | "slabs8" | "skinny8"
+FORCE_FORM = {}             # tests / probes: kind -> form, which wins whenever it is among the candidates.  The kind is the wrapper's ("linear", "to_norm",
+                            # "swiglu") + what the weight source adds: nothing without codes ("skinny" | "gemm" | "slabs"), "8" with w16 and codes (those +
+                            # "gemm8" | "slabs8" | "skinny8"), "c" for a CodesWeight (the three on codes alone); + "i" for the pair "gemm" | "gemm8" of the
+                            # batch-invariant mode with w16 and codes; "linear8t" of linear(keep_bits=True): "skinny" | "skinny8" only
 FORCE_LAYER_FORM = None     # tests / probes: "fused" | "plain" for every row count the fused layer serves
 
 
@@ -447,15 +405,93 @@ def quantize_w8(w: torch.Tensor):
     return w8_pack(codes), scale, w16
 
 
-def _w8_args(w, w8):
-    """The (codes, scale) of weight `w` if this call streams codes: the switch is on and the pair was built for w's shape."""
+# How a projection reads its weight is resolved ONCE per call, into a _WeightSource, and every wrapper below works on that: the 16-bit image,
+# the codes, or both; "8-bit entry, else its 16-bit twin" is one helper (`_launch`), the candidates of the measured forms one table per wrapper
+# (`_form_cands`), their pick one function (`_pick_form`) and the GEMM's tile / schedule one lookup (`_tuned_config`).
+class _WeightSource:
+    """What a projection may stream for its weight: `w16` (the 16-bit tensor, or None), `q` ((codes, scale), or None) and `strict` - codes
+    only (a CodesWeight): an 8-bit entry that does not serve the call is then an error, there being no 16-bit twin to run instead."""
+    __slots__ = ("w16", "q", "strict")
+
+    def __init__(self, w16, q, strict=False):
+        self.w16, self.q, self.strict = w16, q, strict
+
+    shape = property(lambda self: self.w16.shape if self.w16 is not None else self.q[0].shape)
+    kind_suffix = property(lambda self: CODES_KIND_SUFFIX if self.strict else ("8" if self.q is not None else ""))
+    nbytes = property(lambda self: self.w16.numel() * 2 if self.w16 is not None else self.q[0].numel())      # of the image the tuners rotate
+
+    def plain(self) -> "_WeightSource":
+        """The 16-bit image alone (what the forms without an "8" in their name run on)."""
+        return self if self.q is None else _WeightSource(self.w16, None)
+
+    def codes(self) -> "_WeightSource":
+        """The codes alone, still with a 16-bit twin to fall back to elsewhere (not strict): what the GEMM tuner on codes rotates."""
+        return self if self.w16 is None else _WeightSource(None, self.q)
+
+    def clone(self) -> "_WeightSource":
+        """Another copy of the streamed bytes - w16 where there is one, else the codes; the scales are shared.  The tuners rotate through
+        such copies so that none is cache-resident when its turn comes."""
+        if self.w16 is not None:
+            return _WeightSource(self.w16.clone(), self.q)
+        return _WeightSource(None, (self.q[0].clone(), self.q[1]), self.strict)
+
+    def gemm8_ok(self, M, N, K) -> bool:
+        """Is the GEMM on codes a candidate form?  A shape the GEMM takes; beside w16 only up to W8_GEMM_MAX_M rows (in batch-invariant mode
+        too: there `_pick_form` keeps "gemm8" alone of the 8-bit forms, tuned among the W-stream tiles on the data-parallel schedule - the
+        bits of "gemm" on w16 with any tile on that schedule)."""
+        return self.q is not None and K % 128 == 0 and N % 4 == 0 and (self.strict or M <= W8_GEMM_MAX_M)
+
+    def skinny8_ok(self, M, K) -> bool:
+        """Are the weight-streaming kernels on codes a candidate form?  Up to 64 rows, K % 256 == 0 (which the 16-bit kernels take too);
+        never in batch-invariant mode (they split K over waves)."""
+        return self.q is not None and not GEMM_BATCH_INVARIANT and M <= 64 and K % 256 == 0
+
+
+def _rotation(src: _WeightSource, n: int):
+    """`n` copies of a source for a timing run, the caller's own first; one where the device has no room for more."""
+    try:
+        return [src] + [src.clone() for _ in range(n - 1)]
+    except torch.OutOfMemoryError:
+        return [src]
+
+
+def _weight_source(w, w8, x, what: str) -> _WeightSource:
+    """The source of a call's weight, from what the caller passed: a 16-bit tensor, that and w8 = (codes, scale), or a CodesWeight (a
+    source resolved by an outer wrapper passes through).  The switch decides here: with W8_DECODE off a pair is ignored, unvalidated (the
+    16-bit twins on w16: the same model, the same bits), and a CodesWeight raises - before anything is launched or counted."""
+    if isinstance(w, _WeightSource):
+        return w
+    if isinstance(w, CodesWeight):
+        if not W8_DECODE:
+            raise RuntimeError(f"{what}: ops.w8_decode(False) with a codes-only weight - there is no 16-bit weight to stream instead")
+        if x.dtype != w.dtype or x.device != w.device:
+            raise ValueError(f"{what}: activations {x.dtype} on {x.device}, codes-only weight for {w.dtype} on {w.device}")
+        return _WeightSource(None, (w.codes, w.scale), True)
     if w8 is None or not W8_DECODE:
-        return None
+        return _WeightSource(w, None)
     codes, scale = w8
     if codes.dtype != torch.uint8 or scale.dtype != torch.float32 or tuple(codes.shape) != tuple(w.shape) or scale.shape[0] != w.shape[0] \
             or not codes.is_contiguous() or not scale.is_contiguous() or codes.device != w.device:
         raise ValueError("w8 = (uint8 codes [N, K] from quantize_w8, fp32 scale [N]) of the same weight")
-    return codes, scale
+    return _WeightSource(w, (codes, scale))
+
+
+def _launch(src: _WeightSource, what: str, M, N, K, launch8, launch16=None) -> bool:
+    """The one way a projection is launched: its 8-bit entry `launch8(codes_ptr, scale_ptr) -> status` if the source has codes - counted
+    in w8_launches() when it really launched - and, where that entry does not serve the call (_VDD_ERR_UNSUPPORTED: nothing launched),
+    the 16-bit twin `launch16()` on w16, the same model and the same bits; a strict source has no twin and raises.  True: the 8-bit entry
+    ran.  launch16=None: False instead of twin or error - the GEMM, whose tuner skips such a tile and whose wrapper names the config."""
+    if src.q is not None:
+        rc = launch8(src.q[0].data_ptr(), src.q[1].data_ptr())
+        if rc != _VDD_ERR_UNSUPPORTED:
+            _lib.check(rc)
+            _w8_launches[0] += 1
+            return True
+        if launch16 is not None and src.strict:
+            raise ValueError(f"{what}: no kernel on codes serves M={M} N={N} K={K}")
+    if launch16 is not None:
+        launch16()
+    return False
 
 
 # The W-stream tiles of the MFMA GEMM read codes too (vdd_gemm_w8, 17 - 256 rows and the plain layer at any row count up to 256): the tile ids
@@ -467,38 +503,22 @@ W8_GEMM_MAX_M = 256
 
 
 def _w8_form_args(w, w8, M, K, N):
-    """(codes, scale) if the 8-bit GEMM forms are candidates for this projection: codes given, the switch on, M <= W8_GEMM_MAX_M and a
-    shape the GEMM takes.  In batch-invariant mode too: there `_pick_form` keeps "gemm8" alone of the 8-bit forms, and the GEMM on codes
-    is tuned among the W-stream tiles on the data-parallel schedule - the bits of "gemm" on w16 with any tile on that schedule."""
-    q = _w8_args(w, w8)
-    if q is None or M > W8_GEMM_MAX_M or K % 128 != 0 or N % 4 != 0:
-        return None
-    return q
+    """(codes, scale) if the 8-bit GEMM forms are candidates for this projection on w16 + codes (_WeightSource.gemm8_ok), else None."""
+    src = _weight_source(w, w8, None, "w8")
+    return src.q if src.gemm8_ok(M, N, K) else None
 
 
 def _w8_skinny_args(w, w8, M, K):
-    """(codes, scale) if the weight-streaming kernels on codes ("skinny8") are a candidate: codes given, the switch on, a shape the 16-bit
-    kernels take and the 8-bit entries serve (K % 256 == 0), never in batch-invariant mode."""
-    q = _w8_args(w, w8)
-    if q is None or GEMM_BATCH_INVARIANT or not _skinny_serves(M, K) or K % 256 != 0:
-        return None
-    return q
-
-
-def _w8_done(rc) -> bool:
-    """Status of an 8-bit entry: launched (counted), or a shape it does not serve - the caller runs the 16-bit twin on w16, the same
-    model and the same bits."""
-    if rc == _VDD_ERR_UNSUPPORTED:
-        return False
-    _lib.check(rc)
-    _w8_launches[0] += 1
-    return True
+    """(codes, scale) if the weight-streaming kernels on codes ("skinny8") are a candidate on w16 + codes (_WeightSource.skinny8_ok), else None."""
+    src = _weight_source(w, w8, None, "w8")
+    return src.q if src.skinny8_ok(M, K) else None
 
 
 # ---- codes-only weights (load_8bit with w8_only): the quantised weight exists ONLY as e4m3 codes + row scales - no w16 beside them, so weight
-# memory is 1 byte per element + 4 per row.  A CodesWeight goes wherever a projection weight goes; every wrapper then has exactly the forms
-# that read codes - the GEMM on codes (vdd_gemm_codes: any M, the universal form), its slabs, the weight-streaming kernels on codes and the
-# few-row fused entries - measured under kinds and GEMM keys of their own, and raises where none serves the call: nothing falls back to 16 bits.
+# memory is 1 byte per element + 4 per row.  A CodesWeight goes wherever a projection weight goes and resolves to a strict source: the same
+# wrappers, candidate tables and tuners as above, with the forms that read codes alone - the GEMM on codes (vdd_gemm_codes: any M, the universal
+# form), its slabs, the weight-streaming kernels on codes and the few-row fused entries - under kinds ("...c") and GEMM keys of their own, and an
+# error where none serves the call: nothing falls back to 16 bits.
 W8_CODES_TILES = (1, 2, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16)      # vdd_gemm_codes: every tile id but 5 (256 x 192: 12 code images, 8 waves)
 CODES_KIND_SUFFIX = "c"     # form kinds of a CodesWeight: "linearc", "to_normc", "swigluc" ("gemm8" | "slabs8" | "skinny8")
 
@@ -538,127 +558,52 @@ class CodesWeight:
         return w8_dequantize(self.codes, self.scale, self.dtype)
 
 
-def _codes_call(w: CodesWeight, x, what: str):
-    """The checks every call on a CodesWeight makes: the switch (there is no w16 to stream instead) and the operands."""
-    if not W8_DECODE:
-        raise RuntimeError(f"{what}: ops.w8_decode(False) with a codes-only weight - there is no 16-bit weight to stream instead")
-    if x.dtype != w.dtype or x.device != w.device:
-        raise ValueError(f"{what}: activations {x.dtype} on {x.device}, codes-only weight for {w.dtype} on {w.device}")
-    return w.codes, w.scale
-
-
-def _codes_launched(rc, what, M, N, K):
-    """Status of an 8-bit entry on a codes-only weight: launched (counted) - a shape it does not serve is an error here."""
-    if rc == _VDD_ERR_UNSUPPORTED:
-        raise ValueError(f"{what}: no kernel on codes serves M={M} N={N} K={K}")
-    _lib.check(rc)
-    _w8_launches[0] += 1
-
-
-def _pick_codes_form(kind, M, N, K, x, w: CodesWeight, cands, consumer=None):
-    """_pick_form for a CodesWeight: `cands` (name -> fn(CodesWeight)) hold forms on codes only.  Batch-invariant mode: the GEMM on codes
-    (its data-parallel schedule).  Else the measured one, under `kind` (a kind of its own) and timed on rotating copies of the codes."""
-    if not cands:
-        raise ValueError(f"{kind}: no kernel on codes serves M={M} N={N} K={K} (the GEMM on codes takes K % 128 == 0 and N % 4 == 0)")
-    if GEMM_BATCH_INVARIANT and "gemm8" in cands:
-        return "gemm8"
-    if len(cands) == 1:
-        return next(iter(cands))
-    if FORCE_FORM.get(kind) in cands:
-        return FORCE_FORM[kind]
-    key = _form_key(kind, M, N, K, _MODEL_DT[x.dtype])
-    got = _form_choice.get(key)
-    if got is not None and got in cands:
-        return got
-    fallback = "skinny8" if ("skinny8" in cands and M <= FALLBACK_SKINNY_ROWS) else ("gemm8" if "gemm8" in cands else next(iter(cands)))
-    if not GEMM_AUTOTUNE or torch.cuda.is_current_stream_capturing():
-        return fallback
-    n_copies = int(min(24, max(2, -(-640 * 2 ** 20 // w.numel()))))
-    try:
-        copies = [w] + [w.clone() for _ in range(n_copies - 1)]
-    except torch.OutOfMemoryError:
-        copies = [w]
-    run = {n_: (lambda i, f=f: f(copies[i])) for n_, f in cands.items()}
-    if consumer == "norm":
-        res, lnw = torch.zeros(M, N, dtype=x.dtype, device=x.device), torch.ones(N, dtype=x.dtype, device=x.device)
-        thunks = {n_: (lambda i, f=f: rmsnorm(res, lnw, 1e-5, delta=f(i))) for n_, f in run.items()}
-    else:
-        thunks = run
-    got = _pick_timed(key, thunks, x.device, len(copies))
-    return got if got is not None else fallback
-
-
-def _codes_skinny_serves(M, K) -> bool:
-    """The weight-streaming kernels on codes: up to 64 rows, K % 256 == 0; never in batch-invariant mode (they split K over waves)."""
-    return not GEMM_BATCH_INVARIANT and M <= 64 and K % 256 == 0
-
-
 def linear_resid_ss(x, w, resid, out=None, ss=None, w8=None):
     """h = bf16(bf16(x w^T) + resid) (the new residual stream) and ss [M, N/16] fp32: per-block partial sums of squares of h's rows,
     for linear_normed / swiglu_linear_normed.  M <= NORM_FUSED_MAX_M.  w8: (codes, scale) of w (quantize_w8) - streamed instead."""
-    codes_only = isinstance(w, CodesWeight)
-    q = _codes_call(w, x, "linear_resid_ss") if codes_only else None
-    dt = _dt(x, resid) if codes_only else _dt(x, w, resid)
+    src = _weight_source(w, w8, x, "linear_resid_ss")
+    dt = _dt(x, src.w16, resid)
     M, K = x.shape
-    N = w.shape[0]
+    N = src.shape[0]
     out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
     ss = torch.empty(M, (N + 15) // 16, dtype=torch.float32, device=x.device) if ss is None else ss
-    if codes_only:
-        _codes_launched(_lib_ready().vdd_skinny_gemm_resid_ss_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), resid.data_ptr(), out.data_ptr(),
-                                                                 ss.data_ptr(), M, N, K, x.stride(0), resid.stride(0), out.stride(0), dt, _st(x)),
-                        "linear_resid_ss", M, N, K)
-        return out, ss
-    q = _w8_args(w, w8)
-    if q is not None and _w8_done(_lib_ready().vdd_skinny_gemm_resid_ss_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), resid.data_ptr(),
-                                                                            out.data_ptr(), ss.data_ptr(), M, N, K, x.stride(0),
-                                                                            resid.stride(0), out.stride(0), dt, _st(x))):
-        return out, ss
-    _lib.check(_lib_ready().vdd_skinny_gemm_resid_ss(x.data_ptr(), w.data_ptr(), resid.data_ptr(), out.data_ptr(), ss.data_ptr(), M, N, K,
-                                                     x.stride(0), resid.stride(0), out.stride(0), dt, _st(x)))
+    lib = _lib_ready()
+    _launch(src, "linear_resid_ss", M, N, K,
+            lambda cp, sp: lib.vdd_skinny_gemm_resid_ss_w8(x.data_ptr(), cp, sp, resid.data_ptr(), out.data_ptr(), ss.data_ptr(), M, N, K, x.stride(0),
+                                                           resid.stride(0), out.stride(0), dt, _st(x)),
+            lambda: _lib.check(lib.vdd_skinny_gemm_resid_ss(x.data_ptr(), src.w16.data_ptr(), resid.data_ptr(), out.data_ptr(), ss.data_ptr(), M, N, K,
+                                                            x.stride(0), resid.stride(0), out.stride(0), dt, _st(x))))
     return out, ss
 
 
 def linear_normed(h, ss, ln_w, eps, w, out=None, bias=None, w8=None):
     """rmsnorm(h; ln_w, eps) @ w^T with the normalisation done as h's fragments load (h, ss from linear_resid_ss)."""
-    codes_only = isinstance(w, CodesWeight)
-    q = _codes_call(w, h, "linear_normed") if codes_only else None
-    dt = _dt(h, ln_w) if codes_only else _dt(h, w, ln_w)
+    src = _weight_source(w, w8, h, "linear_normed")
+    dt = _dt(h, src.w16, ln_w)
     M, K = h.shape
-    N = w.shape[0]
+    N = src.shape[0]
     out = torch.empty(M, N, dtype=h.dtype, device=h.device) if out is None else out
-    if codes_only:
-        _codes_launched(_lib_ready().vdd_skinny_gemm_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, q[0].data_ptr(),
-                                                               q[1].data_ptr(), out.data_ptr(), M, N, K, h.stride(0), out.stride(0), dt, _st(h)),
-                        "linear_normed", M, N, K)
-        return bias_act(out, bias, out=out) if bias is not None else out
-    q = _w8_args(w, w8)
-    if not (q is not None and _w8_done(_lib_ready().vdd_skinny_gemm_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps,
-                                                                               q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, N, K,
-                                                                               h.stride(0), out.stride(0), dt, _st(h)))):
-        _lib.check(_lib_ready().vdd_skinny_gemm_normed(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, w.data_ptr(), out.data_ptr(),
-                                                       M, N, K, h.stride(0), out.stride(0), dt, _st(h)))
+    lib = _lib_ready()
+    _launch(src, "linear_normed", M, N, K,
+            lambda cp, sp: lib.vdd_skinny_gemm_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, cp, sp, out.data_ptr(), M, N, K,
+                                                         h.stride(0), out.stride(0), dt, _st(h)),
+            lambda: _lib.check(lib.vdd_skinny_gemm_normed(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, src.w16.data_ptr(), out.data_ptr(),
+                                                          M, N, K, h.stride(0), out.stride(0), dt, _st(h))))
     return bias_act(out, bias, out=out) if bias is not None else out
 
 
 def swiglu_linear_normed(h, ss, ln_w, eps, w_gate_up, out=None, w8=None):
-    codes_only = isinstance(w_gate_up, CodesWeight)
-    q = _codes_call(w_gate_up, h, "swiglu_linear_normed") if codes_only else None
-    dt = _dt(h, ln_w) if codes_only else _dt(h, w_gate_up, ln_w)
+    src = _weight_source(w_gate_up, w8, h, "swiglu_linear_normed")
+    dt = _dt(h, src.w16, ln_w)
     M, K = h.shape
-    F = w_gate_up.shape[0] // 2
+    F = src.shape[0] // 2
     out = torch.empty(M, F, dtype=h.dtype, device=h.device) if out is None else out
-    if codes_only:
-        _codes_launched(_lib_ready().vdd_skinny_swiglu_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, q[0].data_ptr(),
-                                                                 q[1].data_ptr(), out.data_ptr(), M, F, K, h.stride(0), dt, _st(h)),
-                        "swiglu_linear_normed", M, 2 * F, K)
-        return out
-    q = _w8_args(w_gate_up, w8)
-    if q is not None and _w8_done(_lib_ready().vdd_skinny_swiglu_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps,
-                                                                            q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, F, K,
-                                                                            h.stride(0), dt, _st(h))):
-        return out
-    _lib.check(_lib_ready().vdd_skinny_swiglu_normed(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, w_gate_up.data_ptr(),
-                                                     out.data_ptr(), M, F, K, h.stride(0), dt, _st(h)))
+    lib = _lib_ready()
+    _launch(src, "swiglu_linear_normed", M, 2 * F, K,
+            lambda cp, sp: lib.vdd_skinny_swiglu_normed_w8(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, cp, sp, out.data_ptr(), M, F, K,
+                                                           h.stride(0), dt, _st(h)),
+            lambda: _lib.check(lib.vdd_skinny_swiglu_normed(h.data_ptr(), ss.data_ptr(), ss.shape[1], ln_w.data_ptr(), eps, src.w16.data_ptr(),
+                                                            out.data_ptr(), M, F, K, h.stride(0), dt, _st(h))))
     return out
 
 
@@ -744,12 +689,37 @@ def _pick_timed(key, thunks, device, n_rot, iters=8):
     return got
 
 
+def _form_cands(src: _WeightSource, forms):
+    """The candidate table of a form wrapper for whatever source it was given.  forms: name ("skinny" | "gemm" | "slabs") -> (eligible on
+    w16, eligible on codes, fn(source, ...)) in the wrapper's own order.  Returns (source, name -> fn(source, ...)): the 16-bit forms under
+    their names - fn on the source's 16-bit image alone - then "gemm8", "slabs8", "skinny8": fn on the source as it is.  Each fn is what
+    `_pick_form` times and what finally runs.  A source whose codes no form can use comes back without them (kind, rotation: as without)."""
+    cands = {}
+    if src.w16 is not None:
+        for name, (ok16, _ok8, fn) in forms.items():
+            if ok16:
+                cands[name] = lambda s, *a, fn=fn: fn(s.plain(), *a)
+    n16 = len(cands)
+    for name in ("gemm", "slabs", "skinny"):
+        if name in forms and forms[name][1]:
+            cands[name + "8"] = forms[name][2]
+    return (src if src.strict or len(cands) > n16 else src.plain()), cands
+
+
 def _pick_form(kind, M, N, K, x, w, cands, consumer=None, w8=None):
-    """Which of `cands` (name -> fn(weight)) runs this [M, K] x [N, K]^T product.  One eligible form: that one.  Batch-invariant mode: the
-    GEMM.  Else the measured one; a product whose consumer is the next RMSNorm is timed WITH that norm (slabs make the norm add S fp32
-    partials: cheaper projection, dearer norm).  w8 = (codes, scale): the candidates whose name ends in "8" are fn(weight, (codes, scale))
-    and are timed on rotating copies of the codes."""
-    if GEMM_BATCH_INVARIANT and "gemm" in cands:
+    """Which of `cands` (name -> fn(source)) runs this [M, K] x [N, K]^T product; w: a 16-bit tensor (w8: its (codes, scale)), a CodesWeight
+    or a resolved source.  One eligible form: that one.  Batch-invariant mode: the GEMM.  Else the measured one; a product whose consumer
+    is the next RMSNorm is timed WITH that norm (slabs make the norm add S fp32 partials: cheaper projection, dearer norm).  Timed on
+    rotating copies of the source: of w16, and of the codes beside it; of the codes alone for a CodesWeight, whose candidates hold forms on
+    codes only, under a kind of its own."""
+    src = _weight_source(w, w8, x, kind)
+    sfx = "8" if src.strict else ""                        # what the shape-generic fallback is called: the 16-bit name wherever there is a w16
+    if src.strict:
+        if not cands:
+            raise ValueError(f"{kind}: no kernel on codes serves M={M} N={N} K={K} (the GEMM on codes takes K % 128 == 0 and N % 4 == 0)")
+        if GEMM_BATCH_INVARIANT and "gemm8" in cands:
+            return "gemm8"                                 # (its data-parallel schedule; no key is read)
+    elif GEMM_BATCH_INVARIANT and "gemm" in cands:
         # one summation order per output element: the GEMM's data-parallel schedule - on w16 or, where measured faster, on the codes (the
         # same bits: a W-stream tile on that schedule).  Measured under a kind of its own (kind + "i"): no tuned-mode entry shares the key
         if "gemm8" not in cands:
@@ -759,27 +729,18 @@ def _pick_form(kind, M, N, K, x, w, cands, consumer=None, w8=None):
         return next(iter(cands))
     if FORCE_FORM.get(kind) in cands:
         return FORCE_FORM[kind]
-    dt = _MODEL_DT[x.dtype]
-    key = _form_key(kind, M, N, K, dt)
+    key = _form_key(kind, M, N, K, _MODEL_DT[x.dtype])
     got = _form_choice.get(key)
     if got is not None and got in cands:
         return got
-    fallback = "skinny" if ("skinny" in cands and M <= FALLBACK_SKINNY_ROWS) else ("gemm" if "gemm" in cands else next(iter(cands)))
+    fallback = "skinny" + sfx if ("skinny" + sfx in cands and M <= FALLBACK_SKINNY_ROWS) else ("gemm" + sfx if "gemm" + sfx in cands else next(iter(cands)))
     if not GEMM_AUTOTUNE or torch.cuda.is_current_stream_capturing():
         return fallback
-    n_copies = int(min(24, max(2, -(-640 * 2 ** 20 // (w.numel() * 2)))))
-    try:
-        copies = [w] + [w.clone() for _ in range(n_copies - 1)]
-    except torch.OutOfMemoryError:
-        copies = [w]
-    if w8 is not None:
-        try:
-            qcopies = [w8] + [(w8[0].clone(), w8[1]) for _ in range(len(copies) - 1)]
-        except torch.OutOfMemoryError:
-            qcopies = [w8]
-        run = {n_: ((lambda i, f=f: f(copies[i], qcopies[i % len(qcopies)])) if n_.endswith("8") else (lambda i, f=f: f(copies[i]))) for n_, f in cands.items()}
-    else:
-        run = {n_: (lambda i, f=f: f(copies[i])) for n_, f in cands.items()}
+    copies = _rotation(src, int(min(24, max(2, -(-640 * 2 ** 20 // src.nbytes)))))
+    if src.w16 is not None and src.q is not None:          # the codes beside w16: as many copies where there is room, else indexed modulo
+        qcopies = _rotation(src.codes(), len(copies))
+        copies = [_WeightSource(c.w16, qcopies[i % len(qcopies)].q) for i, c in enumerate(copies)]
+    run = {n_: (lambda i, f=f: f(copies[i])) for n_, f in cands.items()}
     if consumer == "norm":
         res, lnw = torch.zeros(M, N, dtype=x.dtype, device=x.device), torch.ones(N, dtype=x.dtype, device=x.device)
         thunks = {n_: (lambda i, f=f: rmsnorm(res, lnw, 1e-5, delta=f(i))) for n_, f in run.items()}
@@ -880,12 +841,12 @@ def gemm_workspace_reset(device=None):
             ws[: 4 << 20].zero_()
 
 
-def _gemm_w8_call(x, q, out, bias, M, N, K, epi, config, ws, codes_only=False) -> bool:
-    """vdd_gemm_w8 (codes_only: vdd_gemm_codes) on q = (codes, scale): True = launched (and counted), False = not served (nothing launched,
-    `out` untouched)."""
+def _gemm8_rc(strict, x, codes_ptr, scale_ptr, out, bias, M, N, K, epi, config, ws):
+    """Status of vdd_gemm_w8 - the W-stream tiles, for codes beside a w16 - or, strict, of vdd_gemm_codes - every tile with an 8-bit form, for
+    codes alone (for `_launch`: _VDD_ERR_UNSUPPORTED = nothing launched, `out` untouched)."""
     lib = _lib_ready()
-    return _w8_done((lib.vdd_gemm_codes if codes_only else lib.vdd_gemm_w8)(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                             M, N, K, x.stride(0), out.stride(0), epi, config, ws.data_ptr(), ws.numel(), _MODEL_DT[x.dtype], _st(x)))
+    return (lib.vdd_gemm_codes if strict else lib.vdd_gemm_w8)(x.data_ptr(), codes_ptr, scale_ptr, out.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                                               M, N, K, x.stride(0), out.stride(0), epi, config, ws.data_ptr(), ws.numel(), _MODEL_DT[x.dtype], _st(x))
 
 
 def _gemm_call(x, w, out, bias, resid, M, N, K, epi, config, ws):
@@ -899,87 +860,74 @@ def gemm(x, w, bias=None, resid=None, epi=EPI_NONE, out=None, config=None, w8=No
     """out[M, N] = epilogue(x[M, K] @ w[N, K]^T) on the hand-written MFMA kernel (bf16 or fp16 operands, fp32 accumulate).  epi=EPI_SWIGLU:
     w = [Wgate; Wup], N = w.shape[0] // 2.  No library fallback: unsupported shapes raise.
     w8: (codes, scale) of w (quantize_w8).  With ops.W8_DECODE on and a `config` vdd_gemm_w8 serves, the codes are streamed instead of w -
-    the same bits (include/vdd_hip.h); config=None: tile and schedule tuned among the W-stream tiles under a key of its own; anything the
-    8-bit entry does not serve runs as ever on w."""
-    if isinstance(w, CodesWeight):
-        return _gemm_codes(x, w, bias, resid, epi, out, config)
-    q = _w8_args(w, w8)
-    dt = _dt(x, w, bias, resid)
+    the same bits (include/vdd_hip.h); config=None: tile and schedule tuned among the W-stream tiles under a key of its own (`_tuned_config`);
+    anything the 8-bit entry does not serve runs as ever on w.
+    w a CodesWeight: vdd_gemm_codes - any M, no residual, epilogues NONE / BIAS / SWIGLU; config=None: tuned among W8_CODES_TILES under a key
+    family of its own.  Nothing falls back to 16 bits: a config that entry does not serve raises."""
+    src = _weight_source(w, w8, x, "gemm")
+    dt = _dt(x, src.w16, bias, None if src.strict else resid)          # (codes alone take no residual: refused below, whatever its type)
     M, K = x.shape
-    N = w.shape[0] // 2 if epi == EPI_SWIGLU else w.shape[0]
-    if K % 128 != 0 or N % 4 != 0 or x.stride(1) != 1 or w.stride(1) != 1:
+    N = src.shape[0] // 2 if epi == EPI_SWIGLU else src.shape[0]
+    serves8 = resid is None and epi in (EPI_NONE, EPI_BIAS, EPI_SWIGLU)                   # what the 8-bit entries take
+    if src.strict:
+        if K != src.shape[1] or K % 128 != 0 or N % 4 != 0 or x.stride(1) != 1 or not serves8 or (epi == EPI_SWIGLU and N % 128 != 0):
+            raise ValueError(f"gemm on codes needs K % 128 == 0, N % 4 == 0 (SwiGLU: F % 128 == 0), no residual and the epilogues NONE / BIAS / SWIGLU "
+                             f"(got M={M} N={N} K={K} epi={epi})")
+    elif K % 128 != 0 or N % 4 != 0 or x.stride(1) != 1 or src.w16.stride(1) != 1:
         raise ValueError(f"vdd_gemm needs K % 128 == 0, N % 4 == 0 and K-contiguous operands (got M={M} N={N} K={K})")
     out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
     if M == 0:
         return out
     ws = _gemm_workspace(x.device, M, N)
-    if q is not None and resid is None and epi in (EPI_NONE, EPI_BIAS, EPI_SWIGLU):
-        cfg8 = config if config is not None else (_gemm_w8_config(x, q, out, bias, M, N, K, epi, dt, ws) if M <= W8_GEMM_MAX_M else None)
-        if cfg8 is not None and _gemm_w8_call(x, q, out, bias, M, N, K, epi, cfg8, ws):
+    default = gemm_config(1, 1 if GEMM_BATCH_INVARIANT else 0)         # 256 x 256 tiles, hybrid schedule (batch-invariant mode: data-parallel)
+    if src.q is not None and serves8:
+        cfg8 = config
+        if cfg8 is None and (src.strict or M <= W8_GEMM_MAX_M):
+            cfg8 = _tuned_config((_gemm_key_codes if src.strict else _gemm_key_w8)(M, N, K, epi, dt), default if src.strict else None, x.device, M,
+                                 lambda: _gemm_tune(x, src.codes(), out, bias, None, M, N, K, epi, ws))
+        if cfg8 is not None and _launch(src, "gemm", M, N, K, lambda cp, sp: _gemm8_rc(src.strict, x, cp, sp, out, bias, M, N, K, epi, cfg8, ws)):
             return out
+        if src.strict:
+            raise ValueError(f"gemm on codes: config {cfg8} (tile id {(cfg8 & 15) | ((cfg8 >> 6) << 4)}) is not served for M={M} N={N} K={K} epi={epi}")
     if config is None:
-        key = _gemm_key(M, N, K, epi, dt)
-        config = _gemm_choice.get(key)
-        if config is None and GEMM_AUTOTUNE:
-            _load_persisted(x.device)
-            config = _gemm_choice.get(key)
-        if config is None:
-            config = gemm_config(1, 1) if GEMM_BATCH_INVARIANT else 1
-            if M <= GEMM_TUNE_MAX_M and GEMM_AUTOTUNE:
-                if not torch.cuda.is_current_stream_capturing():
-                    with _CacheLock():                             # one rank of a node tunes, the others read its pick
-                        _read_cache_section()
-                        config = _gemm_choice.get(key)
-                        if config is None:
-                            config = _gemm_choice[key] = _gemm_tune(x, w, out, bias, resid, M, N, K, epi, ws)
-                            _store_persisted(key, config)
-                # (under capture: the default for this launch only - caching it would pin an untuned choice for the process)
-            else:
-                _gemm_choice[key] = config
-    _gemm_call(x, w, out, bias, resid, M, N, K, epi, config, ws)
+        config = _tuned_config(_gemm_key(M, N, K, epi, dt), default, x.device, M,
+                               lambda: _gemm_tune(x, src.plain(), out, bias, resid, M, N, K, epi, ws))
+    _gemm_call(x, src.w16, out, bias, resid, M, N, K, epi, config, ws)
     return out
 
 
-def _gemm_codes(x, w: CodesWeight, bias, resid, epi, out, config):
-    """gemm() on a CodesWeight: vdd_gemm_codes - any M, epilogues NONE / BIAS / SWIGLU.  config=None: tile and schedule tuned among
-    W8_CODES_TILES under a key family of its own (`_gemm_key_codes`); where that cannot be measured (a capture in progress, the tuner off,
-    M above GEMM_TUNE_MAX_M) the 256 x 256 tile, hybrid schedule (batch-invariant mode: data-parallel).  Nothing falls back to 16 bits."""
-    q = _codes_call(w, x, "gemm")
-    dt = _dt(x, bias)
-    M, K = x.shape
-    N = w.shape[0] // 2 if epi == EPI_SWIGLU else w.shape[0]
-    if K != w.shape[1] or K % 128 != 0 or N % 4 != 0 or x.stride(1) != 1 or resid is not None or epi not in (EPI_NONE, EPI_BIAS, EPI_SWIGLU) \
-            or (epi == EPI_SWIGLU and N % 128 != 0):
-        raise ValueError(f"gemm on codes needs K % 128 == 0, N % 4 == 0 (SwiGLU: F % 128 == 0), no residual and the epilogues NONE / BIAS / SWIGLU "
-                         f"(got M={M} N={N} K={K} epi={epi})")
-    out = torch.empty(M, N, dtype=x.dtype, device=x.device) if out is None else out
-    if M == 0:
-        return out
-    ws = _gemm_workspace(x.device, M, N)
-    if config is None:
-        key = _gemm_key_codes(M, N, K, epi, dt)
+def _tuned_config(key, default, device, M, tune):
+    """The GEMM config (tile, schedule) for `key`, looked up in this order: the process table; the persisted tables (in-tree defaults, the
+    cache file - `_load_persisted`); the cache file again under the lock (one rank of a node tunes, the others read its pick); a timing run
+    now, `tune()`, whose result enters the process table and the cache file - unless it is None (no candidate was served): that is neither
+    cached nor stored, and `default` answers.  Where nothing can be measured `default` answers as well: under a graph capture for this
+    launch only (caching it would pin an untuned choice for the process); with the tuner off or M above GEMM_TUNE_MAX_M it is cached
+    under the key.  The three users differ in key family and default alone:
+                                          16-bit                 codes only (CodesWeight)   codes beside w16 (w8=)
+        key                               _gemm_key(.., dt)      dt + 16 (_gemm_key_codes)   dt + 8 (_gemm_key_w8)
+        default                           256 x 256 tile         256 x 256 tile              None: nothing is cached and the answer None
+                                                                                             sends the call to the 16-bit GEMM
+    and the last is consulted only for M <= W8_GEMM_MAX_M, no residual and the epilogues NONE / BIAS / SWIGLU (gemm(), above).  An explicit
+    config= bypasses all of this: the 8-bit entry is tried with it at any row count."""
+    config = _gemm_choice.get(key)
+    if config is None and GEMM_AUTOTUNE:
+        _load_persisted(device)
         config = _gemm_choice.get(key)
-        if config is None and GEMM_AUTOTUNE:
-            _load_persisted(x.device)
-            config = _gemm_choice.get(key)
-        if config is None:
-            config = gemm_config(1, 1) if GEMM_BATCH_INVARIANT else gemm_config(1, 0)
-            if M <= GEMM_TUNE_MAX_M and GEMM_AUTOTUNE:
-                if not torch.cuda.is_current_stream_capturing():
-                    with _CacheLock():
-                        _read_cache_section()
-                        got = _gemm_choice.get(key)
-                        if got is None:
-                            got = _gemm_tune(x, None, out, bias, None, M, N, K, epi, ws, w8=q, codes_only=True)
-                            if got is not None:
-                                _gemm_choice[key] = got
-                                _store_persisted(key, got)
-                        config = got if got is not None else config
-            else:
-                _gemm_choice[key] = config
-    if not _gemm_w8_call(x, q, out, bias, M, N, K, epi, config, ws, codes_only=True):
-        raise ValueError(f"gemm on codes: config {config} (tile id {(config & 15) | ((config >> 6) << 4)}) is not served for M={M} N={N} K={K} epi={epi}")
-    return out
+    if config is not None:
+        return config
+    if M <= GEMM_TUNE_MAX_M and GEMM_AUTOTUNE:
+        if not torch.cuda.is_current_stream_capturing():
+            with _CacheLock():
+                _read_cache_section()
+                config = _gemm_choice.get(key)
+                if config is None:
+                    config = tune()
+                    if config is not None:
+                        _gemm_choice[key] = config
+                        _store_persisted(key, config)
+    elif default is not None:
+        _gemm_choice[key] = default
+    return config if config is not None else default
 
 
 def _gemm_key_codes(M, N, K, epi, dt):
@@ -992,26 +940,6 @@ def _gemm_key_w8(M, N, K, epi, dt):
     """Tuning key of the GEMM on codes: the 16-bit key's buckets with 8 added to the storage type (the last slot: 9 fp16, 10 bf16) - no 16-bit
     entry, persisted or in the process, has such a key, and the cache file's "b,N,K,epi,inv,dt" form carries it as it is."""
     return _gemm_key(M, N, K, epi, dt + 8)
-
-
-def _gemm_w8_config(x, q, out, bias, M, N, K, epi, dt, ws):
-    """Tile / schedule of the GEMM on codes for this shape: the process table, the cache file, or a timing run now; None where it cannot be
-    measured here (the tuner off, a capture in progress) or no W-stream tile serves the call - the caller runs the 16-bit GEMM."""
-    key = _gemm_key_w8(M, N, K, epi, dt)                   # (carries the batch-invariant flag: that mode tunes schedule 1 alone)
-    config = _gemm_choice.get(key)
-    if config is None and GEMM_AUTOTUNE:
-        _load_persisted(x.device)
-        config = _gemm_choice.get(key)
-        if config is None and not torch.cuda.is_current_stream_capturing():
-            with _CacheLock():
-                _read_cache_section()
-                config = _gemm_choice.get(key)
-                if config is None:
-                    config = _gemm_tune(x, None, out, bias, None, M, N, K, epi, ws, w8=q)
-                    if config is not None:
-                        _gemm_choice[key] = config
-                        _store_persisted(key, config)
-    return config
 
 
 GEMM_AUTOTUNE = True            # False: 256 x 256 tiles + the hybrid schedule for every shape (no timing runs at all)
@@ -1212,28 +1140,23 @@ def _store_persisted(key, cfg):
         pass
 
 
-def _gemm_tune(x, w, out, bias, resid, M, N, K, epi, ws, iters=8, w8=None, codes_only=False):
+def _gemm_tune(x, src: _WeightSource, out, bias, resid, M, N, K, epi, ws, iters=8):
     """Times every (tile shape, schedule) candidate on the real operands and keeps the fastest (all write the same result).
     In the decode step a projection's weights always come from HBM (13 GB of them stream through per step), so the timed launches
-    rotate through enough copies of `w` that none is still in the 256-MiB Infinity Cache when its turn comes again: timed on ONE
+    rotate through enough copies of the weight that none is still in the 256-MiB Infinity Cache when its turn comes again: timed on ONE
     hot copy the tuner preferred small macro tiles that then ran 10 % slower in place.
-    w8 = (codes, scale): the GEMM on codes instead (w unused) - the candidates are those of W8_GEMM_TILES, the copies are copies of the
-    codes, and the result is None if the 8-bit entry serves none of them.  codes_only: vdd_gemm_codes and W8_CODES_TILES instead."""
-    src = w if w8 is None else w8[0]
-    n_copies = int(min(24, max(2, -(-640 * 2 ** 20 // (src.numel() * src.element_size())))))
-    try:
-        copies = [src] + [src.clone() for _ in range(n_copies - 1)]
-    except torch.OutOfMemoryError:
-        copies = [src]
-    if w8 is None:
-        def call(wi, cfg):
-            _gemm_call(x, wi, out, bias, resid, M, N, K, epi, cfg, ws)
+    src holds ONE image: w16 - the 16-bit GEMM - or codes - the GEMM on codes instead: the candidates are those of W8_GEMM_TILES (strict,
+    vdd_gemm_codes: W8_CODES_TILES), the copies are copies of the codes, and the result is None if the 8-bit entry serves none of them."""
+    copies = _rotation(src, int(min(24, max(2, -(-640 * 2 ** 20 // src.nbytes)))))
+    if src.q is None:
+        def call(si, cfg):
+            _gemm_call(x, si.w16, out, bias, resid, M, N, K, epi, cfg, ws)
             return True
         candidates, best = GEMM_CANDIDATES, 1
     else:
-        def call(ci, cfg):
-            return _gemm_w8_call(x, (ci, w8[1]), out, bias, M, N, K, epi, cfg, ws, codes_only=codes_only)
-        candidates, best = [(c, s_) for (c, s_) in GEMM_CANDIDATES if c in (W8_CODES_TILES if codes_only else W8_GEMM_TILES)], None
+        def call(si, cfg):
+            return _launch(si, "gemm", M, N, K, lambda cp, sp: _gemm8_rc(src.strict, x, cp, sp, out, bias, M, N, K, epi, cfg, ws))
+        candidates, best = [(c, s_) for (c, s_) in GEMM_CANDIDATES if c in (W8_CODES_TILES if src.strict else W8_GEMM_TILES)], None
     best_t = float("inf")
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     turn = 0
@@ -1276,108 +1199,60 @@ def linear(x, w, out=None, bias=None, w8=None, keep_bits=False):
     w8: (codes, scale) of w - the GEMM and the weight-streaming kernel on codes ("gemm8", "skinny8") join the measurement, under a kind of
     its own.  Forms differ in their summation order, so that measurement may return other low-order bits than the call without codes.
     keep_bits: the codes may only replace w16 INSIDE the form the call without codes takes - where that is "skinny", the twin "skinny8" if
-    measured faster (kind "linear8t": a pair with the same bits) - for a caller that promises the bits of its 16-bit run (the few-row step)."""
+    measured faster (kind "linear8t": a pair with the same bits) - for a caller that promises the bits of its 16-bit run (the few-row step);
+    for a CodesWeight the forms on codes are all there is."""
+    src = _weight_source(w, w8, x, "linear")
     M, K = x.shape
-    N = w.shape[0]
-    if isinstance(w, CodesWeight):                 # (keep_bits: the forms on codes are all there is)
-        _codes_call(w, x, "linear")
-        cands = {}
-        if K % 128 == 0 and N % 4 == 0:
-            cands["gemm8"] = lambda wi: gemm(x, wi)
-        if _codes_skinny_serves(M, K):
-            cands["skinny8"] = lambda wi: skinny_gemm(x, wi)
-        form = _pick_codes_form("linear" + CODES_KIND_SUFFIX, M, N, K, x, w, cands)
-        if form == "skinny8":
-            y = skinny_gemm(x, w, out=out)
-            return bias_act(y, bias, out=y) if bias is not None else y
-        return gemm(x, w, bias=bias, epi=EPI_BIAS if bias is not None else EPI_NONE, out=out)
-    cands = {}
-    if _skinny_serves(M, K):
-        cands["skinny"] = lambda wi: skinny_gemm(x, wi)
-    if K % 128 == 0 and N % 4 == 0:
-        cands["gemm"] = lambda wi: gemm(x, wi)
-    if not cands:
-        raise ValueError(f"linear: no kernel serves M={M} N={N} K={K} (K % 128 == 0 and N % 4 == 0 for the GEMM)")
-    q = _w8_form_args(w, w8, M, K, N)
-    qs = _w8_skinny_args(w, w8, M, K) if "skinny" in cands else None
-    if keep_bits and (q is not None or qs is not None):
-        form, q = _pick_form("linear", M, N, K, x, w, cands), None
-        if form == "skinny" and qs is not None:
-            form = _pick_form("linear8t", M, N, K, x, w, {"skinny": cands["skinny"], "skinny8": lambda wi, qi: skinny_gemm(x, wi, w8=qi)}, w8=qs)
-    else:
-        if q is not None:
-            cands["gemm8"] = lambda wi, qi: gemm(x, wi, w8=qi)
-        if qs is not None:
-            cands["skinny8"] = lambda wi, qi: skinny_gemm(x, wi, w8=qi)
-        q8 = q if q is not None else qs
-        form = _pick_form("linear8" if q8 is not None else "linear", M, N, K, x, w, cands, w8=q8)
-    if form in ("skinny", "skinny8"):
-        y = skinny_gemm(x, w, out=out, w8=qs if form == "skinny8" else None)
+    N = src.shape[0]
+
+    def skinny(s, out=None, bias=None):
+        y = skinny_gemm(x, s, out=out)
         return bias_act(y, bias, out=y) if bias is not None else y
-    return gemm(x, w, bias=bias, epi=EPI_BIAS if bias is not None else EPI_NONE, out=out, w8=q if form == "gemm8" else None)
+    src, cands = _form_cands(src, {
+        "skinny": (_skinny_serves(M, K), src.skinny8_ok(M, K), skinny),
+        "gemm": (K % 128 == 0 and N % 4 == 0, src.gemm8_ok(M, N, K),
+                 lambda s, out=None, bias=None: gemm(x, s, bias=bias, epi=EPI_BIAS if bias is not None else EPI_NONE, out=out))})
+    if not cands and not src.strict:
+        raise ValueError(f"linear: no kernel serves M={M} N={N} K={K} (K % 128 == 0 and N % 4 == 0 for the GEMM)")
+    if keep_bits and src.kind_suffix == "8":
+        form = _pick_form("linear", M, N, K, x, src.plain(), {n_: f for n_, f in cands.items() if not n_.endswith("8")})
+        if form == "skinny" and "skinny8" in cands:
+            form = _pick_form("linear8t", M, N, K, x, src, {"skinny": cands["skinny"], "skinny8": cands["skinny8"]})
+    else:
+        form = _pick_form("linear" + src.kind_suffix, M, N, K, x, src, cands)
+    return cands[form](src, out, bias)
 
 
 def _skinny_swiglu(x, w_gate_up, out=None, w8=None):
+    src = _weight_source(w_gate_up, w8, x, "swiglu_linear")
+    dt = _dt(x, src.w16)
     M, K = x.shape
-    F = w_gate_up.shape[0] // 2
-    if isinstance(w_gate_up, CodesWeight):
-        q = _codes_call(w_gate_up, x, "swiglu_linear")
-        out = torch.empty(M, F, dtype=x.dtype, device=x.device) if out is None else out
-        _codes_launched(_lib_ready().vdd_skinny_swiglu_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, F, K, x.stride(0),
-                                                          _dt(x), _st(x)), "swiglu_linear", M, 2 * F, K)
-        return out
-    q = _w8_args(w_gate_up, w8)
-    dt = _dt(x, w_gate_up)
+    F = src.shape[0] // 2
     out = torch.empty(M, F, dtype=x.dtype, device=x.device) if out is None else out
-    if q is not None and _w8_done(_lib_ready().vdd_skinny_swiglu_w8(x.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), out.data_ptr(), M, F, K, x.stride(0),
-                                                                     dt, _st(x))):
-        return out
-    _lib.check(_lib_ready().vdd_skinny_swiglu(x.data_ptr(), w_gate_up.data_ptr(), out.data_ptr(), M, F, K, x.stride(0), dt, _st(x)))
+    lib = _lib_ready()
+    _launch(src, "swiglu_linear", M, 2 * F, K,
+            lambda cp, sp: lib.vdd_skinny_swiglu_w8(x.data_ptr(), cp, sp, out.data_ptr(), M, F, K, x.stride(0), dt, _st(x)),
+            lambda: _lib.check(lib.vdd_skinny_swiglu(x.data_ptr(), src.w16.data_ptr(), out.data_ptr(), M, F, K, x.stride(0), dt, _st(x))))
     return out
 
 
 def swiglu_linear(x, w_gate_up, out=None, w8=None):
     """silu(x Wg^T) * (x Wu^T) with w_gate_up = [Wg; Wu]: one launch either way - the fused weight-streaming kernel (<= 16 rows: 8 features per
     block; 17 - 64: 16, gate + up tiles) or the MFMA GEMM with the SwiGLU epilogue (no [M, 2F] round trip, no silu_mul launch); measured."""
+    src = _weight_source(w_gate_up, w8, x, "swiglu_linear")
     M, K = x.shape
-    F = w_gate_up.shape[0] // 2
-    if isinstance(w_gate_up, CodesWeight):
-        _codes_call(w_gate_up, x, "swiglu_linear")
-        cands = {}
-        if K % 128 == 0 and F % 128 == 0:
-            cands["gemm8"] = lambda wi, o=None: gemm(x, wi, epi=EPI_SWIGLU, out=o)
-        elif K % 128 == 0 and F % 8 == 0:                   # (odd feature counts: the plain GEMM on codes + vdd_silu_mul)
-            cands["gemm8"] = lambda wi, o=None: silu_mul(gemm(x, wi), out=o)
-        if _codes_skinny_serves(M, K):
-            cands["skinny8"] = lambda wi, o=None: _skinny_swiglu(x, wi, o)
-        form = _pick_codes_form("swiglu" + CODES_KIND_SUFFIX, M, 2 * F, K, x, w_gate_up, {k: (lambda wi, f=f: f(wi)) for k, f in cands.items()})
-        return cands[form](w_gate_up, out)
-    cands = {}
-    if K % 128 == 0 and F % 128 == 0:
-        cands["gemm"] = lambda wi, o=None: gemm(x, wi, epi=EPI_SWIGLU, out=o)
-    elif K % 128 == 0 and F % 8 == 0:                       # (odd feature counts: the plain GEMM + vdd_silu_mul, whose lanes take 8 features)
-        cands["gemm"] = lambda wi, o=None: silu_mul(gemm(x, wi), out=o)
-    if _skinny_serves(M, K):
-        cands["skinny"] = lambda wi, o=None: _skinny_swiglu(x, wi, o)
-    if not cands:
+    F = src.shape[0] // 2
+    if F % 128 == 0:
+        via_gemm = lambda s, out=None: gemm(x, s, epi=EPI_SWIGLU, out=out)
+    else:                                                   # (odd feature counts: the plain GEMM + vdd_silu_mul, whose lanes take 8 features)
+        via_gemm = lambda s, out=None: silu_mul(gemm(x, s), out=out)
+    src, cands = _form_cands(src, {
+        # (beside w16 the GEMM on codes comes with the SwiGLU epilogue only; a CodesWeight takes the plain one + vdd_silu_mul too)
+        "gemm": (K % 128 == 0 and F % 8 == 0, src.gemm8_ok(M, 2 * F, K) and F % (8 if src.strict else 128) == 0, via_gemm),
+        "skinny": (_skinny_serves(M, K), src.skinny8_ok(M, K), lambda s, out=None: _skinny_swiglu(x, s, out))})
+    if not cands and not src.strict:
         raise ValueError(f"swiglu_linear: no kernel serves M={M} F={F} K={K}")
-    _w8_args(w_gate_up, w8)                                                       # (a malformed pair raises whatever the shape)
-    q = _w8_form_args(w_gate_up, w8, M, K, 2 * F) if F % 128 == 0 else None      # (the GEMM on codes: the SwiGLU epilogue only)
-    qs = _w8_skinny_args(w_gate_up, w8, M, K) if "skinny" in cands else None
-    if q is None and qs is None:
-        form = _pick_form("swiglu", M, 2 * F, K, x, w_gate_up, {k: (lambda wi, f=f: f(wi)) for k, f in cands.items()})
-        return cands[form](w_gate_up, out)
-    timed = {k: (lambda wi, f=f: f(wi)) for k, f in cands.items()}
-    if q is not None:
-        timed["gemm8"] = lambda wi, qi: gemm(x, wi, epi=EPI_SWIGLU, w8=qi)
-    if qs is not None:
-        timed["skinny8"] = lambda wi, qi: _skinny_swiglu(x, wi, w8=qi)
-    form = _pick_form("swiglu8", M, 2 * F, K, x, w_gate_up, timed, w8=q if q is not None else qs)
-    if form == "gemm8":
-        return gemm(x, w_gate_up, epi=EPI_SWIGLU, out=out, w8=q)
-    if form == "skinny8":
-        return _skinny_swiglu(x, w_gate_up, out, w8=qs)
-    return cands[form](w_gate_up, out)
+    return cands[_pick_form("swiglu" + src.kind_suffix, M, 2 * F, K, x, src, cands)](src, out)
 
 
 _attn_ws = {}

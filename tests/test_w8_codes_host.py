@@ -1,5 +1,5 @@
 """Codes-only weights (load_8bit with w8_only) without a GPU: what LlavaWeights.quantize_lm_w8(keep_w16=False) leaves behind and what it
-weighs, the ops.CodesWeight handle, which forms the wrappers consider for it (the library calls never reached: `_pick_codes_form` is
+weighs, the ops.CodesWeight handle, which forms the wrappers consider for it (the library calls never reached: `_pick_form` is
 stubbed and records its candidates), the tuning-key family, the 8-byte LDS read of the large tiles restated, and the rule for the two
 committed choices files (stated here too: their `choices` are untouched, their stamps follow the kernel sources)."""
 import json
@@ -114,14 +114,14 @@ class _Stop(Exception):
 
 
 def _candidates(monkeypatch, call):
-    """The (kind, candidate names) a wrapper hands to `_pick_codes_form` - stubbed, so no library call is reached."""
+    """The (kind, candidate names) a wrapper hands to `_pick_form` - stubbed, so no library call is reached."""
     from llava_align_amd import ops
     seen = {}
 
     def pick(kind, M, N, K, x, w, cands, consumer=None):
         seen.update(kind=kind, names=set(cands), consumer=consumer)
         raise _Stop()
-    monkeypatch.setattr(ops, "_pick_codes_form", pick)
+    monkeypatch.setattr(ops, "_pick_form", pick)
     with pytest.raises(_Stop):
         call()
     return seen["kind"], seen["names"]
@@ -168,19 +168,19 @@ def test_pick_codes_form_rules(monkeypatch):
     cw = ops.CodesWeight(torch.zeros(256, 512, dtype=torch.uint8), torch.ones(256), torch.bfloat16)
     f = lambda *a: None
     cands = {"gemm8": f, "slabs8": f, "skinny8": f}
-    assert ops._pick_codes_form("to_normc", 12, 256, 512, x, cw, dict(cands)) == "skinny8"        # the tuner off: the shape-generic fallback
-    assert ops._pick_codes_form("to_normc", 24, 256, 512, x, cw, dict(cands)) == "gemm8"
-    assert ops._pick_codes_form("to_normc", 24, 256, 512, x, cw, {"skinny8": f}) == "skinny8"     # one eligible form: that one
+    assert ops._pick_form("to_normc", 12, 256, 512, x, cw, dict(cands)) == "skinny8"        # the tuner off: the shape-generic fallback
+    assert ops._pick_form("to_normc", 24, 256, 512, x, cw, dict(cands)) == "gemm8"
+    assert ops._pick_form("to_normc", 24, 256, 512, x, cw, {"skinny8": f}) == "skinny8"     # one eligible form: that one
     ops._form_choice[ops._form_key("to_norm8", 24, 256, 512, _lib.VDD_BF16)] = "slabs8"           # a load_8bit=True choice: another kind, not read
-    assert ops._pick_codes_form("to_normc", 24, 256, 512, x, cw, dict(cands)) == "gemm8"
+    assert ops._pick_form("to_normc", 24, 256, 512, x, cw, dict(cands)) == "gemm8"
     ops._form_choice[ops._form_key("to_normc", 24, 256, 512, _lib.VDD_BF16)] = "slabs8"
-    assert ops._pick_codes_form("to_normc", 24, 256, 512, x, cw, dict(cands)) == "slabs8"
+    assert ops._pick_form("to_normc", 24, 256, 512, x, cw, dict(cands)) == "slabs8"
     monkeypatch.setattr(ops, "FORCE_FORM", {"to_normc": "skinny8"})
-    assert ops._pick_codes_form("to_normc", 24, 256, 512, x, cw, dict(cands)) == "skinny8"
+    assert ops._pick_form("to_normc", 24, 256, 512, x, cw, dict(cands)) == "skinny8"
     with ops.batch_invariant():
-        assert ops._pick_codes_form("to_normc", 24, 256, 512, x, cw, dict(cands)) == "gemm8"      # one summation order: forced or measured forms do not count
+        assert ops._pick_form("to_normc", 24, 256, 512, x, cw, dict(cands)) == "gemm8"      # one summation order: forced or measured forms do not count
     with pytest.raises(ValueError, match="M=24 N=256 K=512"):
-        ops._pick_codes_form("to_normc", 24, 256, 512, x, cw, {})                                # nothing serves the call: the shape is named
+        ops._pick_form("to_normc", 24, 256, 512, x, cw, {})                                # nothing serves the call: the shape is named
 
 
 def test_w8_decode_off_raises_for_a_codes_weight():
